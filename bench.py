@@ -15,12 +15,19 @@ child fails) -- the one-command, N-devices form of the reference's ``nn.DataPara
 (wrapper.py:52-68).  Under ``python -m torch.distributed.run --nproc-per-node N ... bench.py --gpus N``
 the environment already carries the rank, and this process IS a rank.
 
-Prints ONE JSON line on rank 0, with
+Prints ONE JSON line on rank 0.  A plain run sets up, warms up, times ``--steps`` steps and prints the headline (``value``,
+``ms_per_step``, the median step, ``ranks_seen`` = world size as seen by the process group after the timing all-reduce).
+``--full`` adds everything else, after the same headline:
   roofline      dominant kernel timed live with HIP events on the launch stream over the timed steps
+  end_to_end    the dense algorithmic work per eval x evals/s against the matrix peaks
+  stages        per-stage times of two more eager steps, every libcmf_amd launch under HIP events
   cpu_baseline  the CPU oracle's reference-equivalent flavour (column loop with primal recompute)
                 timed on this host's cores on a bounded sample (rank 0, N = 1 only)
   f32_exact     (default workload, N = 1) the same step with the 3x3 tangent convs on exact-fp32 MFMA
-  ranks_seen    world size as seen by the process group after the timing all-reduce
+  legs          (default workload) c5, c2b, c5_train, train on one GPU; strong_c3, c5, grad_reduce, train on N > 1
+
+``--dump-outputs DIR`` writes what the last timed step returned (every tensor of the elbo dict; the training path adds the
+loss) as ``DIR/<key>.npy``; the inputs and weights are seeded, so two builds can be compared output for output.
 
 ``--config {c1,c2a,c2b,c5}`` runs the other BASELINE configurations through the same contract.
 """
@@ -69,9 +76,13 @@ def parse_args(argv=None):
     ap.add_argument("--config", choices=sorted(CONFIGS), default="c3", help="BASELINE.json configuration (default: the headline C3)")
     ap.add_argument("--batch", type=int, default=None, help="samples per GPU (weak) or global batch (--strong); default per config")
     ap.add_argument("--strong", action="store_true", help="shard a fixed global batch over the ranks")
-    ap.add_argument("--cpu-batch", type=int, default=None, help="CPU baseline sample size (0 disables); C3: 32 = ~12 s on 16 cores")
-    ap.add_argument("--no-kernel-timer", action="store_true")
-    ap.add_argument("--no-f32-exact", action="store_true", help="skip the exact-fp32 leg of the default C3 run")
+    ap.add_argument("--full", action="store_true", help="also take the secondary figures (roofline, end_to_end, stages, cpu_baseline, "
+                                                         "f32_exact and the legs); a plain run times the headline only")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="write the last timed step's outputs as DIR/<key>.npy "
+                                                                         "(float32 / float64, at most 64 MB in all)")
+    ap.add_argument("--cpu-batch", type=int, default=None, help="--full: CPU baseline sample size (0 disables); C3: 32 = ~12 s on 16 cores")
+    ap.add_argument("--no-kernel-timer", action="store_true", help="--full: no HIP events in the timed region (no roofline, no stages)")
+    ap.add_argument("--no-f32-exact", action="store_true", help="--full: skip the exact-fp32 leg of the default C3 run")
     ap.add_argument("--graph", action="store_true", help="replay the step from a captured HIP graph (default for the launch-bound "
                                                           "c1 / c2a / c2b); the roofline leg then comes from separate eager steps")
     ap.add_argument("--no-graph", action="store_true", help="c1 / c2a / c2b: time eager launches instead of graph replays")
@@ -86,8 +97,8 @@ def parse_args(argv=None):
     ap.add_argument("--backend", default="nccl", help="torch.distributed backend (nccl = RCCL; gloo only to rehearse N > 1 "
                                                        "on a one-GPU box together with --share-gpu)")
     ap.add_argument("--share-gpu", action="store_true", help="rehearsal: every rank uses cuda:0 (never a measurement)")
-    ap.add_argument("--no-legs", action="store_true", help="default C3 run only: skip the secondary measurements (N = 1: c5, c2b, "
-                                                            "c5_train, train; N > 1: strong_c3, c5)")
+    ap.add_argument("--no-legs", action="store_true", help="--full default C3 run only: skip the secondary measurements (N = 1: c5, "
+                                                            "c2b, c5_train, train; N > 1: strong_c3, c5)")
     ap.add_argument("--leg-steps", type=int, default=10, help="timed steps of each secondary measurement")
     ap.add_argument("--train-batch", type=int, default=64, help="samples per GPU of the C3 training leg (64 = the reference's per-GPU "
                                                                  "shard, BASELINE configs[3]; smaller only to rehearse many ranks on one GPU)")
@@ -279,6 +290,35 @@ def cpu_model():
     return platform.processor() or platform.machine()
 
 
+def dump_outputs(out, directory, limit=64 << 20):
+    """``--dump-outputs``: every tensor of ``out`` (nested dict keys joined by '.') as ``directory/<key>.npy``, float64 kept and
+    every other dtype written as float32.  Should the arrays exceed ``limit`` bytes in all, each one larger than an equal share
+    of it is replaced by a fixed, seeded sample of that many of its flattened elements (in index order).  Returns the keys."""
+    import numpy as np
+    import torch
+    arrays = {}
+
+    def walk(prefix, v):
+        if isinstance(v, dict):
+            for k, x in v.items():
+                walk(f"{prefix}.{k}" if prefix else str(k), x)
+        elif isinstance(v, torch.Tensor):
+            t = v.detach()
+            arrays[prefix.replace(os.sep, "_")] = t.to(torch.float64 if t.dtype == torch.float64 else torch.float32).cpu().numpy()
+
+    walk("", out)
+    if sum(a.nbytes for a in arrays.values()) > limit:
+        share = limit // len(arrays)
+        for k, a in arrays.items():
+            if a.nbytes > share:
+                idx = np.random.default_rng(0).choice(a.size, share // a.itemsize, replace=False)
+                arrays[k] = a.reshape(-1)[np.sort(idx)]
+    os.makedirs(directory, exist_ok=True)
+    for k, a in arrays.items():
+        np.save(os.path.join(directory, k + ".npy"), a)
+    return sorted(arrays)
+
+
 #: libcmf_amd symbol -> stage of the per-stage breakdown (calls inside FlowProgram.encode all count as "encode")
 STAGE_OF = {"cmf_conv_tangent_bf16x3": "tangent_hidden", "cmf_conv_tangent": "tangent_first_last",
             "cmf_conv_tangent_f16x3": "primal", "cmf_conv_tangent:primal": "primal", "cmf_conv_tangent_bf16x3:primal": "primal",
@@ -378,10 +418,11 @@ def grad_reduce_leg(n, rank, world, device, iters=20, warmup=3):
                     "not overlapped with it (a 24 MB bucket against a 185 ms step)"}
 
 
-def train_leg(steps, warmup, config, density, x, B, rank, world, device, off=True, reduce_shape="all_reduce"):
+def train_leg(steps, warmup, config, density, x, B, rank, world, device, off=True, reduce_shape="all_reduce", dump=None):
     """Secondary metric: training samples / s (one process per GPU, flat gradient all-reduce over RCCL, fused Adam).  C3: the
     Cholesky objective with the off-diagonal metric term; C5: train mode selects the Hutchinson + CG surrogate
-    (non_square.py:131-138), whose backward runs through the 2 S probe directions.  Returns the result object (rank 0) or None."""
+    (non_square.py:131-138), whose backward runs through the 2 S probe directions.  ``dump``: directory for rank 0's
+    ``dump_outputs`` of the last timed step (loss + elbo dict).  Returns the result object (rank 0) or None."""
     import torch
     import torch.distributed as dist
     from cmf_amd.optim import FlatOptimizer
@@ -389,13 +430,14 @@ def train_leg(steps, warmup, config, density, x, B, rank, world, device, off=Tru
     opt = FlatOptimizer(density.parameters(), opt="adam", lr=1e-4, reduce_shape=reduce_shape)
     kw = dict(add_reconstruction=True, add_offdiagonal_metric_reg=off, likelihood_wt=1., metric_wt=1.)
 
-    def step():
+    def step(keep=False):
         opt.zero_grad()
-        loss = -density.elbo(x, **kw)["elbo"].mean()
+        out = density.elbo(x, **kw)
+        loss = -out["elbo"].mean()
         loss.backward()
         opt.allreduce_flat()
         opt.step()
-        return loss.detach()
+        return (out if keep else None), loss.detach()      # (a kept dict holds its autograd graph: the last step's only)
 
     def fence():
         if world > 1:
@@ -407,13 +449,16 @@ def train_leg(steps, warmup, config, density, x, B, rank, world, device, off=Tru
         step()
     fence()
     t0 = time.perf_counter()
-    for _ in range(steps):
-        loss = step()
+    for i in range(steps):
+        out, loss = step(keep=bool(dump) and i == steps - 1)
     fence()
     dt = torch.tensor([time.perf_counter() - t0], device=device, dtype=torch.float64)
     if world > 1:
         dist.all_reduce(dt, op=dist.ReduceOp.MAX)
     dt = float(dt.item())
+    if dump and rank == 0:
+        dump_outputs({"loss": loss, **out}, dump)
+    del out
     density.eval()
     peak = torch.cuda.max_memory_allocated(device) / 2 ** 30
     del opt
@@ -552,14 +597,17 @@ class Workload:
 
 def eval_timed(wl, world, steps, warmup, timer_select=None, graph=None, grouped=None):
     """W untimed + K timed ``elbo`` steps bracketed by barrier + synchronize; returns (max-over-ranks seconds, last loss,
-    per-kernel HIP-event rows or None, world size the process group reported)."""
+    per-kernel HIP-event rows or None, world size the process group reported).  The last timed step's elbo dict is left in
+    ``wl.last_out`` (graph replays: the graph's own buffers, valid until the next replay)."""
     import torch
     import torch.distributed as dist
     from cmf_amd import engine as E
     from cmf_amd.distributed import allreduce_mean_elbo
 
-    def step():
+    def step(keep=False):
         out = graph(wl.x) if graph is not None else wl.inner.elbo(wl.x, **wl.kw)
+        if keep:
+            wl.last_out = out
         return allreduce_mean_elbo(out["elbo"])          # (sum, count) all-reduce; plain mean on one rank
 
     grouped = world > 1 if grouped is None else grouped
@@ -581,7 +629,7 @@ def eval_timed(wl, world, steps, warmup, timer_select=None, graph=None, grouped=
             t0 = time.perf_counter()
             marks[0].record()
             for i in range(steps):
-                loss = step()
+                loss = step(keep=i == steps - 1)
                 marks[i + 1].record()
             fence()
             dt = time.perf_counter() - t0
@@ -707,7 +755,7 @@ def run_rank(args):
         density.train()                                      # non_square.py:131-138: train mode selects hutch_with_cg
 
     if args.train:
-        line = train_leg(args.steps, args.warmup, args.config, inner, x, B, rank, world, device, off)
+        line = train_leg(args.steps, args.warmup, args.config, inner, x, B, rank, world, device, off, dump=args.dump_outputs)
         if rank == 0:
             print(json.dumps(line), flush=True)
         if grouped:
@@ -726,18 +774,23 @@ def run_rank(args):
                 graph, graph_note = None, "HIP-graph capture failed on another rank: every rank times eager launches"
         args.graph = graph is not None
 
-    # the headline keeps its round-1 definition: only the dominant kernel family carries events inside the timed region
+    # --full: the headline keeps its round-1 definition, only the dominant kernel family carries events inside the timed region
     select = None
-    if not args.no_kernel_timer and graph is None:
+    if args.full and not args.no_kernel_timer and graph is None:
         select = (lambda name: name == HIDDEN_CONV) if args.config in ("c3", "c5") else (lambda name: True)
     dt, loss, rows, seen = eval_timed(wl, world, args.steps, args.warmup, select, graph, grouped)
     per_step = sorted(wl.step_ms)                            # the headline's own steps (later legs re-use ``wl``)
-    if graph is not None and not args.no_kernel_timer:       # replayed graphs cannot carry events: eager steps, outside the timed region
+    last_out = wl.__dict__.pop("last_out")
+    if args.dump_outputs and rank == 0:
+        dump_outputs(last_out, args.dump_outputs)
+    del last_out
+    if args.full and graph is not None and not args.no_kernel_timer:   # replayed graphs cannot carry events: eager steps, after the timed region
         _, _, rows, _ = eval_timed(wl, world, 3, 1, lambda name: True, None)
 
     # secondary measurements of the default command (SURVEY 8d "Secondary: train-mode fwd+bwd steps/s; per-stage times"; VERDICT r2
     # items 3 / 4): same process (group), after the headline's timed region, each with its own barrier + synchronize bracket
-    default_run = (args.config == "c3" and not args.strong and not args.hutchinson and not args.no_legs and args.precision == "bf16x3")
+    default_run = (args.full and args.config == "c3" and not args.strong and not args.hutchinson and not args.no_legs
+                   and args.precision == "bf16x3")
     legs = {}
     if default_run and world > 1:
         # BASELINE configs[3]: the SAME global batch of 512 sharded over the ranks; configs[4]: CIFAR d=128, 32 samples per GPU
@@ -748,7 +801,7 @@ def run_rank(args):
                                      graph=True, primal=args.primal_precision)
         legs["c5"] = eval_leg("c5", 32, rank, world, device, args.leg_steps, 1, args.precision, "weak", graph=True, primal=args.primal_precision)
     stages = None
-    if rank == 0 and not args.train and not args.no_kernel_timer and not args.hutchinson:
+    if args.full and rank == 0 and not args.train and not args.no_kernel_timer and not args.hutchinson:
         stages = guarded("stages", lambda: stages_leg(wl, 1e3 * dt / args.steps), 1)
     if default_run and world > 1:
         # the gradient bucket's two reduction shapes, then the reference's actual multi-GPU workload (DataParallel TRAINING, 64
@@ -821,7 +874,8 @@ def run_rank(args):
         n_ = len(per_step)
         line["ms_per_step_median"] = per_step[n_ // 2] if n_ % 2 else 0.5 * (per_step[n_ // 2 - 1] + per_step[n_ // 2])
         line["ms_per_step_minmax"] = [per_step[0], per_step[-1]]
-        line["end_to_end"] = end_to_end(args.config, B * world * args.steps / dt, args.precision, inner)
+        if args.full:
+            line["end_to_end"] = end_to_end(args.config, B * world * args.steps / dt, args.precision, inner)
         if stages is not None:
             line["stages"] = stages
         if args.force_group:
@@ -833,7 +887,7 @@ def run_rank(args):
         for k, v in legs.items():
             if v is not None:
                 line[k] = v
-        if world == 1 and args.cpu_batch > 0:
+        if args.full and world == 1 and args.cpu_batch > 0:
             line["cpu_baseline"] = guarded("cpu_baseline", lambda: cpu_baseline(schema, shape, {k: v.cpu() for k, v in sd.items()},
                                                                                 args.cpu_batch, dataset, off, label), 1)
         line["printed_at_unix"] = time.time()               # (a launcher test bounds the teardown: process-group destruction, exit)

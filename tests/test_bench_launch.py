@@ -35,6 +35,9 @@ def test_rank_environment_is_honoured(monkeypatch):
     assert args.gpus == 4 and args.batch == 4096 and args.steps == 20 and args.cpu_batch == 4096
     args = bench.parse_args([])
     assert (args.gpus, args.steps, args.warmup, args.batch, args.config) == (1, 3, 1, 512, "c3")
+    assert args.full is False and args.dump_outputs is None                    # a plain run times the headline only
+    args = bench.parse_args(["--steps", "7", "--full", "--dump-outputs", "out"])
+    assert args.steps == 7 and args.full is True and args.dump_outputs == "out"
     called = {}
     monkeypatch.setenv("WORLD_SIZE", "4")
     monkeypatch.setattr(bench, "spawn_ranks", lambda *a: called.setdefault("spawn", True))
@@ -66,6 +69,28 @@ def test_a_failing_rank_stops_its_siblings_and_a_deadline_bounds_the_launch(tmp_
     ok = tmp_path / "ok.py"
     ok.write_text("import os\nif os.environ['RANK'] == '0':\n    print('{\"value\": 1}')\n")
     assert bench.spawn_ranks(bench.parse_args(["--gpus", "2"]), [], script=str(ok)) == 0
+
+
+def test_dump_outputs_writes_float_arrays_within_the_limit(tmp_path):
+    """bench.dump_outputs (``--dump-outputs``): every tensor of the nested elbo dict as <dotted key>.npy, float64 kept and other
+    dtypes as float32; over the byte limit, the arrays above an equal share become the same seeded sample on every call."""
+    import numpy as np
+    import torch
+    sys.path.insert(0, ROOT)
+    import bench
+    out = {"elbo": torch.arange(6, dtype=torch.float32).view(6, 1), "steps": 3,
+           "prior-dict": {"low-dim-x": torch.arange(12, dtype=torch.float64).view(6, 2), "mask": torch.tensor([True, False])}}
+    assert bench.dump_outputs(out, str(tmp_path / "a")) == ["elbo", "prior-dict.low-dim-x", "prior-dict.mask"]
+    a = {k: np.load(tmp_path / "a" / f"{k}.npy") for k in ("elbo", "prior-dict.low-dim-x", "prior-dict.mask")}
+    assert a["elbo"].dtype == np.float32 and a["elbo"].shape == (6, 1) and a["elbo"][5, 0] == 5
+    assert a["prior-dict.low-dim-x"].dtype == np.float64 and np.array_equal(a["prior-dict.low-dim-x"], np.arange(12.).reshape(6, 2))
+    assert a["prior-dict.mask"].dtype == np.float32 and a["prior-dict.mask"].tolist() == [1, 0]
+    big = {"big": torch.arange(10000, dtype=torch.float32), "small": torch.ones(4)}
+    for d in ("b", "c"):
+        bench.dump_outputs(big, str(tmp_path / d), limit=4000)
+    b, c = np.load(tmp_path / "b" / "big.npy"), np.load(tmp_path / "c" / "big.npy")
+    assert b.shape == (500,) and np.array_equal(b, c) and np.all(np.diff(b) > 0) and b.max() < 10000
+    assert np.array_equal(np.load(tmp_path / "b" / "small.npy"), np.ones(4, np.float32))
 
 
 def test_a_failing_secondary_measurement_does_not_cost_the_line(capsys):

@@ -366,7 +366,7 @@ def test_bench_contract_line():
     batch so that it takes seconds."""
     import json, os, subprocess, sys
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    out = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--steps", "1", "--warmup", "1",
+    out = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--steps", "1", "--warmup", "1", "--full",
                           "--batch", "32", "--cpu-batch", "8", "--leg-steps", "1"], capture_output=True, text=True, timeout=900)
     assert out.returncode == 0, out.stderr[-2000:]
     lines = [l for l in out.stdout.splitlines() if l.strip()]
@@ -419,6 +419,34 @@ def test_bench_contract_line():
     assert "graph" in d["c5"]["config"]["workload"] and "eager steps" in d["c5"]["roofline"]["note"]      # round 5: the small shard replays a graph
     assert d["c5_train"]["config"]["peak_memory_gib"] < 30 and "Hutchinson" in d["c5_train"]["config"]["workload"]
     assert "kernel source" in (d["roofline"].get("traffic_source") or "")
+
+
+def test_bench_plain_line_and_reproducible_outputs(tmp_path):
+    """A plain run (no --full) prints the headline only, over exactly --steps timed steps; --dump-outputs writes the last timed
+    step's elbo dict, and two runs with the same arguments write the same arrays (seeded inputs and weights)."""
+    import json, os, subprocess, sys
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    lines, dumps = [], []
+    for run in ("a", "b"):
+        out = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--steps", "2", "--warmup", "1",
+                              "--batch", "16", "--dump-outputs", str(tmp_path / run)], capture_output=True, text=True, timeout=900)
+        assert out.returncode == 0, out.stderr[-2000:]
+        got = [l for l in out.stdout.splitlines() if l.strip()]
+        assert len(got) == 1
+        lines.append(json.loads(got[0]))
+        dumps.append({f[:-4]: np.load(tmp_path / run / f) for f in sorted(os.listdir(tmp_path / run))})
+    d = lines[0]
+    assert d["steps"] == 2 and d["warmup"] == 1 and d["n_gpus"] == 1 and d["higher_is_better"] is True and d["unit"] == "evals/s"
+    assert d["metric"].startswith("log-density evals/sec") and d["dtype"].startswith("f32")
+    assert d["value"] > 0 and abs(d["value"] - 16 / (d["ms_per_step"] * 1e-3)) / d["value"] < 1e-6
+    for k in ("roofline", "end_to_end", "stages", "cpu_baseline", "f32_exact", "c5", "c2b", "c5_train", "train"):
+        assert k not in d, k
+    a, b = dumps
+    assert set(a) == set(b) and "elbo" in a and a["elbo"].shape == (16, 1) and a["elbo"].dtype == np.float32
+    assert all(v.dtype in (np.float32, np.float64) for v in a.values()) and sum(v.nbytes for v in a.values()) <= 64 << 20
+    assert abs(float(a["elbo"].astype(np.float64).mean()) - d["config"]["loss_mean"]) <= 1e-5 * abs(d["config"]["loss_mean"])
+    for k in a:
+        assert np.array_equal(a[k], b[k]), k
 
 
 @pytest.mark.parametrize("name", ALL)

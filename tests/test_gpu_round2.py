@@ -310,7 +310,7 @@ def _bench(*argv, timeout=900):
 def test_bench_launches_two_ranks_from_a_bare_shell():
     """``python bench.py --gpus 2`` with no launcher around it: the parent spawns the ranks (gloo + one shared GPU here: a
     rehearsal of the RCCL launch on a one-GPU box), relays ONE JSON line, world size as the process group saw it."""
-    line = _bench("--gpus", "2", "--backend", "gloo", "--share-gpu", "--batch", "32", "--steps", "1", "--warmup", "1",
+    line = _bench("--gpus", "2", "--backend", "gloo", "--share-gpu", "--batch", "32", "--steps", "1", "--warmup", "1", "--full",
                   "--cpu-batch", "0", "--leg-steps", "1")        # (the training leg at the reference's 64 samples per rank)
     assert line["n_gpus"] == 2 and line["ranks_seen"] == 2
     assert line["config"]["global_batch"] == 64 and line["scaling"] == "weak"
@@ -336,7 +336,7 @@ def test_bench_launches_two_ranks_from_a_bare_shell():
 
 @pytest.mark.parametrize("config", ["c1", "c2b"])
 def test_bench_other_configs_print_the_contract(config):
-    line = _bench("--config", config, "--steps", "3", "--cpu-batch", "64")
+    line = _bench("--config", config, "--steps", "3", "--cpu-batch", "64", "--full")
     for key in ("metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better", "scaling",
                 "vs_baseline", "dtype", "data", "config", "roofline", "cpu_baseline"):
         assert key in line, key

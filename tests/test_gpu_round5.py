@@ -293,7 +293,7 @@ def test_bench_launches_four_ranks_from_a_bare_shell_and_tears_down():
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "LOCAL_WORLD_SIZE", "MASTER_ADDR", "MASTER_PORT")}
     t0 = time.time()
     r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "4", "--backend", "gloo", "--share-gpu", "--batch", "8",
-                        "--steps", "1", "--warmup", "1", "--leg-steps", "1", "--train-batch", "8", "--cpu-batch", "0"],
+                        "--steps", "1", "--warmup", "1", "--full", "--leg-steps", "1", "--train-batch", "8", "--cpu-batch", "0"],
                        capture_output=True, text=True, env=env, timeout=1500, cwd=root)
     t_exit = time.time()
     assert r.returncode == 0, r.stderr[-3000:]
