@@ -36,3 +36,18 @@ __device__ __forceinline__ float block_sum(float v, float* red) {
   for (int i = 0; i < nw; ++i) t += red[i];
   return t;
 }
+
+// head_wide.hip: the Jacobian head for 128 < nc <= 512 (d <= 512); dispatch targets of the C entry points, arguments validated there
+int cmf_wide_gram_cholesky(const float* t, long long t_b, long long t_r, int n_rows, int d, int B, float* jtj, float* logdet,
+                           float* l1_off, float* l1_diag, int* info, int* fail, hipStream_t s);
+int cmf_wide_cholesky_retry(float* jtj, int d, int B, int attempt, float eps, float* logdet, float* l1_diag, int* info, int* fail,
+                            hipStream_t s);
+int cmf_wide_gram_backward(const float* t, long long t_b, long long t_r, int n_rows, int nc, int d, int B, const float* jtj,
+                           const float* g_logdet, const float* g_l1off, const float* g_l1diag, float* dt, long long dt_b,
+                           long long dt_r, float* ws, hipStream_t s);
+int cmf_wide_gram_backward_matrix(const float* t, long long t_b, long long t_r, int n_rows, int nc, int d, int B, const float* m,
+                                  float* dt, long long dt_b, long long dt_r, hipStream_t s);
+int cmf_wide_hutch_cg(const float* jtj, const float* eps, int d, int S, int B, int max_iter, int min_iter, float tol, float* u,
+                      float* w, float* val, int* iters, hipStream_t s);
+int cmf_wide_hutch_cotangent(const float* u, const float* eps, const float* w, int d, int S, int B, const float* g_val,
+                             const float* g_off, const float* g_diag, float* M, hipStream_t s);

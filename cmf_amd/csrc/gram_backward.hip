@@ -122,8 +122,9 @@ extern "C" int cmf_gram_backward(const float* t, long long t_b, long long t_r, i
 extern "C" int cmf_gram_backward_matrix(const float* t, long long t_b, long long t_r, int n_rows, int nc, int d, int B,
                                         const float* m, float* dt, long long dt_b, long long dt_r, void* stream) {
   if (!t || !m || !dt) return CMF_EINVAL;
-  if (n_rows <= 0 || B <= 0 || d <= 0 || d > nc || nc % 16 || nc > 128) return CMF_EINVAL;
+  if (n_rows <= 0 || B <= 0 || d <= 0 || d > nc || nc % 16 || nc > 512) return CMF_EINVAL;
   if ((t_b | t_r | dt_b | dt_r) % 4 || (uintptr_t)t % 16 || (uintptr_t)dt % 16) return CMF_EINVAL;
+  if (nc > 128) return cmf_wide_gram_backward_matrix(t, t_b, t_r, n_rows, nc, d, B, m, dt, dt_b, dt_r, (hipStream_t)stream);
   const size_t lds = ((size_t)d * (nc + 4) + 2 * nc + (size_t)SLAB * nc) * sizeof(float);
   if (lds > 48 * 1024) {
     hipError_t e = cmf_set_dynamic_lds((const void*)gram_backward_kernel, (int)lds);
@@ -133,4 +134,16 @@ extern "C" int cmf_gram_backward_matrix(const float* t, long long t_b, long long
                      (const float*)nullptr, (const float*)nullptr, (const float*)nullptr, dt, dt_b, dt_r, m);
   CMF_LAUNCH_CHECK();
   return 0;
+}
+
+extern "C" int cmf_gram_backward_ws(const float* t, long long t_b, long long t_r, int n_rows, int nc, int d, int B,
+                                    const float* jtj, const float* g_logdet, const float* g_l1off, const float* g_l1diag,
+                                    float* dt, long long dt_b, long long dt_r, float* ws, void* stream) {
+  if (nc <= 128)
+    return cmf_gram_backward(t, t_b, t_r, n_rows, nc, d, B, jtj, g_logdet, g_l1off, g_l1diag, dt, dt_b, dt_r, stream);
+  if (!t || !jtj || !dt || !ws) return CMF_EINVAL;
+  if (n_rows <= 0 || B <= 0 || d <= 0 || d > nc || nc % 16 || nc > 512) return CMF_EINVAL;
+  if ((t_b | t_r | dt_b | dt_r) % 4 || (uintptr_t)t % 16 || (uintptr_t)dt % 16) return CMF_EINVAL;
+  return cmf_wide_gram_backward(t, t_b, t_r, n_rows, nc, d, B, jtj, g_logdet, g_l1off, g_l1diag, dt, dt_b, dt_r, ws,
+                                (hipStream_t)stream);
 }

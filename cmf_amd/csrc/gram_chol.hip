@@ -638,13 +638,14 @@ extern "C" int cmf_gram_cholesky(const float* t, long long t_b, long long t_r, i
                                  float* jtj, float* logdet, float* l1_off, float* l1_diag, int* info, int* fail,
                                  void* stream) {
   if (!t || !jtj || !logdet || !l1_off || !l1_diag || !info || !fail) return CMF_EINVAL;
-  if (n_rows <= 0 || B <= 0 || d <= 0 || d > nc || nc % 16 || nc > 128) return CMF_EINVAL;
+  if (n_rows <= 0 || B <= 0 || d <= 0 || d > nc || nc % 16 || nc > 512) return CMF_EINVAL;
   if ((t_b | t_r) % 4 || (uintptr_t)t % 16) return CMF_EINVAL;
   hipStream_t s = (hipStream_t)stream;
   // A kernel node, not hipMemsetAsync: a captured 32-byte memset node replayed with garbage from the second
   // hipGraphLaunch on (ROCm 7.2, observed as pointer-like values in the flags), which silently armed every retry.
   hipLaunchKernelGGL(zero_flags_kernel, dim3(1), dim3(64), 0, s, fail);
   CMF_LAUNCH_CHECK();
+  if (nc > 128) return cmf_wide_gram_cholesky(t, t_b, t_r, n_rows, d, B, jtj, logdet, l1_off, l1_diag, info, fail, s);
 #ifdef CMF_DBG_GRAMOLD
   if (nc == 64) return launch_gram_direct<4>(t, t_b, t_r, n_rows, d, B, jtj, logdet, l1_off, l1_diag, info, fail, s);
 #endif
@@ -672,10 +673,11 @@ extern "C" int cmf_gram_cholesky(const float* t, long long t_b, long long t_r, i
 
 extern "C" int cmf_cholesky_retry(float* jtj, int d, int B, int attempt, float eps0, float* logdet, float* l1_diag,
                                   int* info, int* fail, void* stream) {
-  if (!jtj || !logdet || !l1_diag || !info || !fail || d <= 0 || d > 128 || B <= 0 || attempt < 1 || attempt > 7)
+  if (!jtj || !logdet || !l1_diag || !info || !fail || d <= 0 || d > 512 || B <= 0 || attempt < 1 || attempt > 7)
     return CMF_EINVAL;
   float eps = eps0;
   for (int i = 1; i < attempt; ++i) eps *= 10.f;
+  if (d > 128) return cmf_wide_cholesky_retry(jtj, d, B, attempt, eps, logdet, l1_diag, info, fail, (hipStream_t)stream);
   const size_t lds = (size_t)d * (d + 1) * sizeof(float);
   if (lds > 48 * 1024) {
     hipError_t e = cmf_set_dynamic_lds((const void*)chol_retry_kernel, (int)lds);

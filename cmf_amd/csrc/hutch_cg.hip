@@ -22,6 +22,8 @@
 // grid-wide barrier per iteration.  With the reference's default tolerance of 1 (relative residuals start at 1) both
 // rules stop at the minimum count in practice; for d <= 11 that is max_iter = d iterations, i.e. the exact solve.
 // The source is not vendored under /root/reference, so the iterates stay PARITY-UNPINNED.
+//
+// d > 128 or S > 128 dispatches to hutch_wide_kernel (head_wide.hip), whose header argues the explicit form for d up to 512.
 #include "common.h"
 
 namespace {
@@ -236,7 +238,7 @@ __global__ void hutch_lowrank_cotangent_kernel(const float* __restrict__ w, int 
 
 extern "C" int cmf_hutch_lowrank_cotangent(const float* w, int d, int S, int B, const float* g_val, const float* g_diag, int n,
                                            float* cmat, void* stream) {
-  if (!cmat || d <= 0 || d > 128 || S <= 0 || S > 128 || B <= 0) return CMF_EINVAL;
+  if (!cmat || d <= 0 || d > 512 || S <= 0 || S > 512 || B <= 0) return CMF_EINVAL;
   const int K = g_diag ? (d < S ? d : S) : 0;
   if (n != 2 * S + K || (g_diag && !w)) return CMF_EINVAL;
   const long long total = (long long)B * n * n;
@@ -248,8 +250,10 @@ extern "C" int cmf_hutch_lowrank_cotangent(const float* w, int d, int S, int B, 
 
 extern "C" int cmf_hutch_cg(const float* jtj, const float* eps, int d, int S, int B, int max_iter, int min_iter, float tol,
                             float* u, float* w, float* val, int* iters, void* stream) {
-  if (!jtj || !eps || !u || !w || !val || !iters || d <= 0 || d > 128 || S <= 0 || S > 128 || B <= 0 || max_iter <= 0)
+  if (!jtj || !eps || !u || !w || !val || !iters || d <= 0 || d > 512 || S <= 0 || S > 512 || B <= 0 || max_iter <= 0)
     return CMF_EINVAL;
+  if (d > 128 || S > 128)
+    return cmf_wide_hutch_cg(jtj, eps, d, S, B, max_iter, min_iter, tol, u, w, val, iters, (hipStream_t)stream);
   const int Sl = S < 16 ? S : 16, chunks = (S + 15) / 16;
   const size_t lds = (size_t)(d * (d + 1) + 4 * Sl * d + Sl) * sizeof(float);      // <= 66 + 32 KB
   hipStream_t s = (hipStream_t)stream;
@@ -272,7 +276,7 @@ extern "C" int cmf_hutch_cg(const float* jtj, const float* eps, int d, int S, in
 }
 
 extern "C" int cmf_hutch_metric(const float* w, int d, int S, int B, float* l1_off, float* l1_diag, void* stream) {
-  if (!w || d <= 0 || d > 128 || S <= 0 || S > 128 || B <= 0 || (!l1_off && !l1_diag)) return CMF_EINVAL;
+  if (!w || d <= 0 || d > 512 || S <= 0 || S > 512 || B <= 0 || (!l1_off && !l1_diag)) return CMF_EINVAL;
   if (l1_off && S != d) return CMF_EINVAL;                       // non_square.py:98: the off-diagonal view needs a square block
   hipLaunchKernelGGL(hutch_metric_kernel, dim3(B), dim3(256), 0, (hipStream_t)stream, w, d, S, l1_off, l1_diag);
   CMF_LAUNCH_CHECK();
@@ -281,9 +285,10 @@ extern "C" int cmf_hutch_metric(const float* w, int d, int S, int B, float* l1_o
 
 extern "C" int cmf_hutch_cotangent(const float* u, const float* eps, const float* w, int d, int S, int B, const float* g_val,
                                    const float* g_off, const float* g_diag, float* M, void* stream) {
-  if (!u || !eps || !M || d <= 0 || d > 128 || S <= 0 || S > 128 || B <= 0) return CMF_EINVAL;
+  if (!u || !eps || !M || d <= 0 || d > 512 || S <= 0 || S > 512 || B <= 0) return CMF_EINVAL;
   if ((g_off || g_diag) && !w) return CMF_EINVAL;
   if (g_off && S != d) return CMF_EINVAL;
+  if (d > 128 || S > 128) return cmf_wide_hutch_cotangent(u, eps, w, d, S, B, g_val, g_off, g_diag, M, (hipStream_t)stream);
   const size_t lds = (size_t)2 * d * (S + 1) * sizeof(float);
   if (lds > 48 * 1024) {
     hipError_t e = cmf_set_dynamic_lds((const void*)hutch_cotangent_kernel, (int)lds);

@@ -862,6 +862,7 @@ class NonSquareHeadDensity(Density):
             assert add_reconstruction and want_lik
         chunk = B
         if want_jac:
+            E.check_latent_width(prog.d)                 # before the encode: a head that cannot run launches nothing
             per = prog.tangent_bytes_per_sample(E.ceil16(prog.d))
             chunk = max(1, min(B, prog.TANGENT_BUDGET // max(per, 1)))
             if chunk < B:
@@ -1028,6 +1029,8 @@ class NonSquareHeadDensity(Density):
         d-column sweep that feeds the explicit Gram matrix then runs WITHOUT saved state, and a second, n-column sweep seeded
         with V = [u | eps (| e_k for the diagonal metric term)] is the one kept for the backward pass."""
         E.require_gpu(z_low)
+        if tangents:
+            E.check_latent_width(self.program.d)
         with torch.no_grad():
             low = self._hutch_lowrank_columns(add_diag, add_off) if (tangents and hutch_eps is not None) else None
             if low is not None:

@@ -705,12 +705,26 @@ def channel_sum_batched(ts, t_np, t_c, t_px, np_, Cc, npx, nc, outs, t_sl=16):
                                                    int(nc), _stream()), "cmf_channel_sum_batched")
 
 
+#: widest Jacobian the head kernels take (column slots ceil16(d) <= 512); up to 128 the d x d matrix stays in LDS, wider runs
+#: csrc/head_wide.hip
+MAX_LATENT = 512
+WIDE_NC = 128
+
+
+def check_latent_width(d):
+    """Raise before any launch when the Jacobian head cannot take d columns (sampling and latent extraction need no head)."""
+    if not 1 <= int(d) <= MAX_LATENT:
+        raise ValueError(f"latent_dimension = {int(d)}: the Jacobian head (Gram, Cholesky, Hutchinson kernels) supports "
+                         f"1 <= latent_dimension <= {MAX_LATENT}")
+
+
 class GramResult:
     __slots__ = ("jtj", "logdet", "l1_off", "l1_diag", "info", "fail", "attempts")
 
 
 def gram_cholesky(T, d, max_attempts=6, eps0=1e-6):
     """Fused Gram + Cholesky with the reference's whole-batch jitter retries enqueued back to back."""
+    check_latent_width(d)
     lib = _lib.load()
     dev = T.data.device
     r = GramResult()
@@ -726,8 +740,12 @@ def gram_cholesky(T, d, max_attempts=6, eps0=1e-6):
     TIMER = _timer()
     if TIMER is None:
         launch()
-    else:                                          # 2 D d^2 (+ d^3/3) FLOP and (D NC + d^2 + 3) 4 B per sample
+    elif T.nc <= WIDE_NC:                          # 2 D d^2 (+ d^3/3) FLOP and (D NC + d^2 + 3) 4 B per sample
         TIMER.wrap("gram_cholesky", T.B * (2.0 * T.N * d * d + d ** 3 / 3.0), 4.0 * T.B * (T.N * T.nc + d * d + 3), launch)
+    else:                                          # head_wide.hip: the lower-triangle tiles (half the products) and the
+        nt = -(-d // 64)                           # factorisation's passes over jtj (l1 sums, panels, trailing updates, restore)
+        TIMER.wrap("gram_cholesky_wide", T.B * (2.0 * T.N * d * d + d ** 3 / 3.0),
+                   4.0 * T.B * (nt * (nt + 1) // 2 * 2 * 64 * T.N + 4 * d * d + d ** 3 / 96.0), launch)
     cholesky_retries(r, d, max_attempts, eps0)
     return r
 
@@ -735,6 +753,7 @@ def gram_cholesky(T, d, max_attempts=6, eps0=1e-6):
 def cholesky_retries(r, d, max_attempts=6, eps0=1e-6):
     """Enqueue the whole-batch jitter retries 1 .. max_attempts-1 behind a factorisation (non_square.py:280-288): retry ``a``
     exits at once unless ``fail[a-1]`` is set, else adds eps0 * 10^(a-1) to every sample's diagonal IN PLACE and factorises again."""
+    check_latent_width(d)
     lib = _lib.load()
     B = r.jtj.shape[0]
     for a in range(1, max_attempts):
@@ -747,8 +766,23 @@ def gram_backward(T, jtj, g_logdet=None, g_l1off=None, g_l1diag=None):
     g_l1diag (each (B,) or None): what autograd yields through non_square.py:307-308, :280-294, :87-100."""
     B, d = jtj.shape[0], jtj.shape[1]
     assert B == T.B and d <= T.nc
+    check_latent_width(d)
     dT = T.like(T.N)
     gs = [None if g is None else g.to(torch.float32).contiguous() for g in (g_logdet, g_l1off, g_l1diag)]
+    if T.nc > WIDE_NC:
+        # G^-1 from a Cholesky factorisation in a workspace (factor + the d x d cotangent): torch-allocated, so a captured
+        # graph's pool serves it
+        ws = torch.empty(2 * B * d * d, dtype=torch.float32, device=T.data.device)
+        launch = lambda: _lib.check(_lib.load().cmf_gram_backward_ws(
+            _p(T.data), T.t_b, T.t_r, T.N, T.nc, d, B, _p(jtj), *[None if g is None else _p(g) for g in gs], _p(dT.data), dT.t_b,
+            dT.t_r, _p(ws), _stream()), "cmf_gram_backward_ws")
+        TIMER = _timer()
+        if TIMER is None:
+            launch()
+        else:                                      # factor d^3/3, inverse ~d^3, product 2 D NC d; panel in and out, 4 d^2 of ws
+            TIMER.wrap("gram_backward_wide", B * (d ** 3 * 4 / 3.0 + 2.0 * T.N * T.nc * d),
+                       4.0 * B * (2 * T.N * T.nc + 6 * d * d), launch)
+        return dT
     _lib.check(_lib.load().cmf_gram_backward(_p(T.data), T.t_b, T.t_r, T.N, T.nc, d, B, _p(jtj),
                                              *[None if g is None else _p(g) for g in gs], _p(dT.data), dT.t_b, dT.t_r,
                                              _stream()), "cmf_gram_backward")
@@ -759,23 +793,38 @@ def gram_backward_matrix(T, M):
     """dT = T (M + M^T) for an explicit cotangent M (B, d, d) of the Gram matrix (Hutchinson surrogate training)."""
     B, d = M.shape[0], M.shape[1]
     assert B == T.B and d <= T.nc
+    check_latent_width(d)
     dT = T.like(T.N)
-    _lib.check(_lib.load().cmf_gram_backward_matrix(_p(T.data), T.t_b, T.t_r, T.N, T.nc, d, B, _p(M.to(torch.float32).contiguous()),
-                                                    _p(dT.data), dT.t_b, dT.t_r, _stream()), "cmf_gram_backward_matrix")
+    Mc = M.to(torch.float32).contiguous()
+    launch = lambda: _lib.check(_lib.load().cmf_gram_backward_matrix(_p(T.data), T.t_b, T.t_r, T.N, T.nc, d, B, _p(Mc), _p(dT.data),
+                                                                     dT.t_b, dT.t_r, _stream()), "cmf_gram_backward_matrix")
+    TIMER = _timer()
+    if TIMER is None or T.nc <= WIDE_NC:
+        launch()
+    else:
+        TIMER.wrap("gram_backward_matrix_wide", 2.0 * B * T.N * T.nc * d, 4.0 * B * (2 * T.N * T.nc + 2 * d * d), launch)
     return dT
 
 
 def hutch_cg(jtj, eps, max_iter, tol, min_iter=None):
     """Hutchinson surrogate on explicit J^T J: returns (value (B,), u, w (B,d,S), iterations (B,))."""
     B, d, S = eps.shape
+    check_latent_width(d)
     if min_iter is None:
         min_iter = min(10, max_iter - 1) + 1 if max_iter > 1 else 1
     dev = eps.device
     u, w = torch.empty_like(eps), torch.empty_like(eps)
     val = torch.empty(B, dtype=torch.float32, device=dev)
     iters = torch.empty(B, dtype=torch.int32, device=dev)
-    _lib.check(_lib.load().cmf_hutch_cg(_p(jtj), _p(eps.contiguous()), d, S, B, int(max_iter), int(min_iter), float(tol),
-                                        _p(u), _p(w), _p(val), _p(iters), _stream()), "cmf_hutch_cg")
+    ec = eps.contiguous()
+    launch = lambda: _lib.check(_lib.load().cmf_hutch_cg(_p(jtj), _p(ec), d, S, B, int(max_iter), int(min_iter), float(tol), _p(u),
+                                                         _p(w), _p(val), _p(iters), _stream()), "cmf_hutch_cg")
+    TIMER = _timer()
+    if TIMER is None or (d <= WIDE_NC and S <= WIDE_NC):
+        launch()
+    else:                                          # per iteration (at most max_iter) one G read per 16-probe chunk
+        TIMER.wrap("hutch_cg_wide", 2.0 * B * d * d * S * (max_iter + 1),
+                   4.0 * B * d * d * -(-S // 16) * (max_iter + 1), launch)
     return val, u, w, iters
 
 
@@ -784,6 +833,7 @@ def hutch_metric(w):
     off-diagonal sum exists only for S == d (the reference's ``view`` at :98; None otherwise); the diagonal one is
     ``torch.diagonal`` of the rectangular block: min(d, S) entries (:87-92)."""
     B, d, S = w.shape
+    check_latent_width(d)
     off = torch.empty(B, dtype=torch.float32, device=w.device) if S == d else None
     diag = torch.empty(B, dtype=torch.float32, device=w.device)
     _lib.check(_lib.load().cmf_hutch_metric(_p(w.contiguous()), d, S, B, _p(off), _p(diag), _stream()), "cmf_hutch_metric")
@@ -793,10 +843,17 @@ def hutch_metric(w):
 def hutch_cotangent(u, eps, w, g_val=None, g_off=None, g_diag=None):
     """d objective / d (J^T J) as an explicit (B, d, d) matrix for the train-mode Hutchinson objective (u detached)."""
     B, d, S = eps.shape
+    check_latent_width(d)
     M = torch.empty(B, d, d, dtype=torch.float32, device=eps.device)
     gs = [None if g is None else g.to(torch.float32).contiguous() for g in (g_val, g_off, g_diag)]
-    _lib.check(_lib.load().cmf_hutch_cotangent(_p(u.contiguous()), _p(eps.contiguous()), _p(w.contiguous()), d, S, B,
-                                               *[None if g is None else _p(g) for g in gs], _p(M), _stream()), "cmf_hutch_cotangent")
+    uc, ec, wc = u.contiguous(), eps.contiguous(), w.contiguous()
+    launch = lambda: _lib.check(_lib.load().cmf_hutch_cotangent(_p(uc), _p(ec), _p(wc), d, S, B, *[None if g is None else _p(g) for g in gs],
+                                                                _p(M), _stream()), "cmf_hutch_cotangent")
+    TIMER = _timer()
+    if TIMER is None or (d <= WIDE_NC and S <= WIDE_NC):
+        launch()
+    else:
+        TIMER.wrap("hutch_cotangent_wide", 2.0 * B * d * d * S, 4.0 * B * (3 * d * S + d * d), launch)
     return M
 
 
@@ -804,6 +861,7 @@ def hutch_lowrank_cotangent(w, S, g_val=None, g_diag=None):
     """(B, n, n) cotangent of P^T P for the n-column sweep P = J [u | eps | e_0..e_{K-1}] of the low-rank Hutchinson backward
     (``cmf_hutch_lowrank_cotangent``); n = 2 S + (min(d, S) if g_diag is given)."""
     B, d = w.shape[0], w.shape[1]
+    check_latent_width(d)
     n = 2 * S + (min(d, S) if g_diag is not None else 0)
     M = torch.empty(B, n, n, dtype=torch.float32, device=w.device)
     gs = [None if g is None else g.to(torch.float32).contiguous() for g in (g_val, g_diag)]

@@ -290,7 +290,10 @@ int cmf_seed_tangent(float* t, long long t_b, long long t_r, const int* col_of, 
  *   fail  int32[8]: fail[a] != 0 iff attempt a failed for ANY sample (whole-batch retry, :284-288)
  * cmf_gram_cholesky is attempt 0.  cmf_cholesky_retry(attempt = a >= 1) returns immediately on the
  * device unless fail[a-1] != 0; otherwise it adds eps * 10^(a-1) to the diagonal of EVERY sample's
- * jtj (in place) and refactorises.  The host may enqueue all retries without synchronising.       */
+ * jtj (in place) and refactorises.  The host may enqueue all retries without synchronising.
+ * Widths: nc % 16 == 0, d <= nc <= 512 (cmf_cholesky_retry: d <= 512).  nc <= 128 keeps the whole matrix in LDS; 128 < nc runs
+ * head_wide.hip (Gram on a (tile, sample) grid, blocked factorisation in global memory that restores jtj afterwards, so jtj is
+ * exactly symmetric and intact on return).  Wider: CMF_EINVAL.                                                              */
 int cmf_gram_cholesky(const float* t, long long t_b, long long t_r, int n_rows, int nc, int d, int B,
                       float* jtj, float* logdet, float* l1_off, float* l1_diag, int* info, int* fail,
                       void* stream);
@@ -304,7 +307,13 @@ int cmf_cholesky_retry(float* jtj, int d, int B, int attempt, float eps0, float*
 int cmf_gram_backward(const float* t, long long t_b, long long t_r, int n_rows, int nc, int d, int B,
                       const float* jtj, const float* g_logdet, const float* g_l1off, const float* g_l1diag,
                       float* dt, long long dt_b, long long dt_r, void* stream);
-/* The same product for an EXPLICIT cotangent m [B][d][d] of the Gram matrix (not necessarily symmetric):
+/* The same for any width nc <= 512 with a caller-owned workspace ws of 2 * B * d * d floats (G^-1 for 128 < nc comes from a
+ * Cholesky factorisation of jtj in ws, and the d x d cotangent lives beside it).  nc <= 128 runs cmf_gram_backward (ws unused);
+ * cmf_gram_backward itself keeps nc <= 128.  No allocation, no synchronisation.                                              */
+int cmf_gram_backward_ws(const float* t, long long t_b, long long t_r, int n_rows, int nc, int d, int B,
+                         const float* jtj, const float* g_logdet, const float* g_l1off, const float* g_l1diag,
+                         float* dt, long long dt_b, long long dt_r, float* ws, void* stream);
+/* The same product for an EXPLICIT cotangent m [B][d][d] of the Gram matrix (not necessarily symmetric), any nc <= 512:
  * dt = t (m + m^T).  Training on the Hutchinson surrogate (non_square.py:203-258): m = mean_s u_s eps_s^T, u detached.   */
 int cmf_gram_backward_matrix(const float* t, long long t_b, long long t_r, int n_rows, int nc, int d, int B,
                              const float* m, float* dt, long long dt_b, long long dt_r, void* stream);
@@ -332,15 +341,17 @@ int cmf_elbo_combine(const float* low, const float* logdet, const float* rec, co
  * cmf_gram_cholesky (see hutch_cg.hip for why the explicit form is the cheaper one on this hardware):
  *   w(b,:,s) = G(b) eps(b,:,s);  u = CG(G, eps) with x0 = 0, unit-normalised right-hand sides, at least
  *   min_iter and at most max_iter iterations, stopping a sample when the mean over its S probes of the
- *   relative residual 2-norm drops below tol;  val[b] = mean_s sum_k u*w.   eps, u, w: [B][d][S]; S <= 128
+ *   relative residual 2-norm drops below tol;  val[b] = mean_s sum_k u*w.   eps, u, w: [B][d][S]; S <= 512
  *   (probes beyond 16 run in chunks of 16 with the stopping rule applied per chunk; iters[b] = the slowest chunk).
- * The reference's solver (gpytorch linear_cg @ fc2053b) is un-vendored: CG iterates are parity-unpinned. */
+ * d, S <= 512; d > 128 or S > 128 runs the kernel of head_wide.hip, which reads jtj as a SYMMETRIC matrix (as cmf_gram_cholesky
+ * writes it).  The reference's solver (gpytorch linear_cg @ fc2053b) is un-vendored: CG iterates are parity-unpinned. */
 int cmf_hutch_cg(const float* jtj, const float* eps, int d, int S, int B, int max_iter, int min_iter, float tol,
                  float* u, float* w, float* val, int* iters, void* stream);
 /* Metric term on the Hutchinson product W = (J^T J) eps, [B][d][S] with S == d -- the third return value of
  * non_square.py:253-258 fed to :87-100:  l1_diag[b] = sum_k |W_kk|,  l1_off[b] = sum_{i != j} |W_ij|
  * (the reference's masked_select(~eye).view(B, d(d-1)) exists only for S == d: l1_off must be NULL otherwise; the diagonal branch,
  * torch.diagonal of the (B, d, S) product at :87-92, is valid for any S and sums min(d, S) entries).  Either output may be NULL. */
+/* d, S <= 512 here and in the two cotangent entry points below. */
 int cmf_hutch_metric(const float* w, int d, int S, int B, float* l1_off, float* l1_diag, void* stream);
 /* Cotangent of the Gram matrix for the train-mode Hutchinson objective, u detached (non_square.py:236-247):
  *   M(b) = g_val[b]/S sum_s u_s eps_s^T + sum_s (g_off[b] [i != s] + g_diag[b] [i == s]) sign(W_is) e_i eps_s^T,
