@@ -11,6 +11,8 @@ the reference's (B, C, H, W) layout and carries ALL d Jacobian columns of a samp
 (column-innermost tangent tensors), so each coupler-network layer is a single MFMA kernel launch
 for the whole batch and all columns, followed by the fused Gram + Cholesky + log-det kernel.
 """
+import numbers
+
 import numpy as np
 import torch
 import torch.nn as nn
@@ -273,10 +275,46 @@ def _scoped(fn):
     import functools
 
     @functools.wraps(fn)
-    def run(self, *args, **kwargs):
-        with E.scope(self.head.kernels), E._lib.phase(fn.__name__):      # (``head``: a weak proxy, see FlowProgram.__init__)
+    def run(self, *args, kernels=None, **kwargs):
+        # ``kernels=``: an explicit KernelConfig for this call instead of the head's (the precision guard's re-run); an outer
+        # ``scope`` cannot do it, this one is innermost
+        with E.scope(self.head.kernels if kernels is None else kernels), E._lib.phase(fn.__name__):   # (``head``: a weak proxy)
             return fn(self, *args, **kwargs)
     return run
+
+
+class PrecisionGuard:
+    """Opt-in precision guard of a head's no-grad log-density path (``head.precision_guard = PrecisionGuard()``).
+
+    After the Cholesky factorisation every sample's kappa_1(J^T J) is computed on the device (``engine.gram_condition``, exact in
+    float64) and left in ``head.last_gram.cond``.  With ``head.check_cholesky == "sync"`` the samples above ``max_condition`` are
+    evaluated again -- encode, decode, Gram, Cholesky, combine -- on the ``fallback`` kernel configuration (default: exact fp32
+    tangent and primal convolutions), and their rows replace the default ones in every output and in ``last_gram``; the rows
+    that ran twice are listed in ``last_gram.recomputed``.  ``"lazy"`` (and ``ElboGraph``) only records the estimate.
+
+    max_condition  samples with cond > max_condition are re-run (+inf: never; 0: always).  The default is the crossover measured
+                   on the full-size MNIST model (profiles/precision_envelope.txt) divided by 10.
+    fallback       an ``engine.KernelConfig``.
+
+    Not guarded: the autograd path (``elbo`` with gradients, ``train_forward``, ``loss_and_gradients``) and the train-mode
+    Hutchinson estimator -- they run exactly as without a guard."""
+    __slots__ = ("max_condition", "fallback")
+
+    DEFAULT_MAX_CONDITION = 6.5e6       # profiles/precision_envelope.txt: the default config holds 1e-4 up to kappa_1 6.5e7, / 10
+
+    def __init__(self, max_condition=DEFAULT_MAX_CONDITION, fallback=None):
+        if isinstance(max_condition, bool) or not isinstance(max_condition, numbers.Real):
+            raise TypeError(f"max_condition must be a real number, got {max_condition!r}")
+        mc = float(max_condition)
+        if not mc >= 0.0:
+            raise ValueError(f"max_condition must be >= 0 (inf: never re-run), got {max_condition!r}")
+        fallback = E.KernelConfig(tangent="f32", primal="f32") if fallback is None else fallback
+        if not isinstance(fallback, E.KernelConfig):
+            raise TypeError(f"fallback must be an engine.KernelConfig, got {type(fallback).__name__}")
+        self.max_condition, self.fallback = mc, fallback
+
+    def __repr__(self):
+        return f"PrecisionGuard(max_condition={self.max_condition!r}, fallback={self.fallback!r})"
 
 
 class FlowProgram:
@@ -325,6 +363,11 @@ class FlowProgram:
 
     #: False: every coupling layer runs its whole network whatever it is fed (rounds 1 - 4; the A/B switch of the bit-identity tests)
     SKIP_STRUCTURAL_ZEROS = True
+
+    def depends_on_kernel_config(self):
+        """True when some coupling network of the program runs convolutions whose arithmetic ``KernelConfig`` picks (the 3x3 convs
+        of ResNet couplers); MLP-coupler programs (C1, C2) compute the same numbers under every configuration."""
+        return any(isinstance(m, AffineCouplingBijection) and m.net.kind == "resnet" for m in self.layers + self.prior)
 
     def _structural_zeros(self):
         """Which coupling layers of the DECODE sweep read nothing but structural zeros: {layer index in ``self.layers``: True}.
@@ -761,6 +804,15 @@ class NonSquareTailDensity(Density):
         return self.prior.extract_latent(x, **kwargs)
 
 
+def _scatter_rows(dst, rows, src):
+    """dst[rows] = src along dim 0 for every tensor of a (nested) result dict, in place."""
+    for k, v in dst.items():
+        if isinstance(v, dict):
+            _scatter_rows(v, rows, src[k])
+        else:
+            v.index_copy_(0, rows, src[k])
+
+
 def _cat_nested(outs):
     """Concatenate the result dicts of sub-batches along dim 0, recursing into nested dicts."""
     first = outs[0]
@@ -823,6 +875,8 @@ class NonSquareHeadDensity(Density):
         #: arithmetic of this head's convolution kernels (engine.KernelConfig: tangent "bf16x3" | "f32", primal "f16x3" | "f32" |
         #: "bf16x3"); a plain attribute -- not a parameter or buffer, not in the state dict
         self.kernels = E.KernelConfig()
+        #: opt-in ``PrecisionGuard`` of the no-grad Cholesky path (None: off); a plain attribute like ``kernels``
+        self.precision_guard = None
         self._program = None
         self.last_gram = None
 
@@ -880,17 +934,19 @@ class NonSquareHeadDensity(Density):
             return outs[0]
         return _cat_nested(outs)
 
-    def _elbo_chunk(self, x, want_lik, want_jac, add_rec, add_diag, add_off, lw, mw, ood, pre):
+    def _elbo_chunk(self, x, want_lik, want_jac, add_rec, add_diag, add_off, lw, mw, ood, pre, kernels=None):
+        """One sub-batch of the no-grad path.  ``kernels``: the configuration of the precision guard's re-run (None: the head's)."""
         prog, B, dev = self.program, x.shape[0], x.device
         x = x.contiguous()
         if self.nested_prior_dict:
-            z_low, low_elbo, _, prior_dict = prog.encode_nested(x)
+            z_low, low_elbo, _, prior_dict = prog.encode_nested(x, kernels=kernels)
         else:
-            z_low, low_elbo, _ = prog.encode(x)
+            z_low, low_elbo, _ = prog.encode(x, kernels=kernels)
             prior_dict = {"elbo": low_elbo.view(B, 1), "low-dim-x": z_low}
         logdet = l1 = None
+        rerun = None
         if want_jac:
-            x_hat, T = prog.decode(z_low, tangents=True)
+            x_hat, T = prog.decode(z_low, tangents=True, kernels=kernels)
             hutch = self.training and self.log_jacobian_method == "hutch_with_cg"
             # the Hutchinson branch never factorises (non_square.py:203-258): no jitter may touch its Gram matrix
             g = E.gram_cholesky(T, prog.d, 1 if hutch else self.MAX_ATTEMPTS)
@@ -906,18 +962,44 @@ class NonSquareHeadDensity(Density):
                     l1_off, l1_diag = E.hutch_metric(w)
                     l1 = l1_diag if add_diag else l1_off
             else:
-                self._report_attempts(g)
+                guard = self.precision_guard
+                if guard is not None:
+                    E.gram_condition(g, prog.d, guard.max_condition)
+                flagged = self._report_attempts(g)
+                if flagged is not None and kernels is None:
+                    # sync mode: re-run the flagged rows on the fallback kernels, unless no layer's arithmetic depends on the
+                    # configuration (or the fallback is the head's own): the numbers would come out the same
+                    same = (guard.fallback.tangent, guard.fallback.primal) == (self.kernels.tangent, self.kernels.primal)
+                    if flagged and prog.depends_on_kernel_config() and not same:
+                        rerun = g.flagged_idx[:flagged].long()
+                    g.recomputed = rerun if rerun is not None else torch.empty(0, dtype=torch.int64, device=dev)
                 logdet = g.logdet
                 l1 = g.l1_diag if add_diag else (g.l1_off if add_off else None)
         else:
-            x_hat, _ = prog.decode(z_low, tangents=False)      # warm-up: decode only (non_square.py:105-109)
+            x_hat, _ = prog.decode(z_low, tangents=False, kernels=kernels)      # warm-up: decode only (non_square.py:105-109)
         rec = E.recon_sqerr(x_hat, x) if add_rec else None
         if ood:
             lik = E.elbo_combine(low_elbo, logdet, None, None, None, 1.0, 0.0, 0.0, B, dev)
-            return {"likelihood": lik, "reconstruction-error": rec.view(B, 1)}
-        elbo = E.elbo_combine(low_elbo if want_lik else None, logdet, rec, l1, pre, lw, self.regularization_param, mw,
-                              B, dev)
-        return {"elbo": elbo, "prior-dict": prior_dict}
+            out = {"likelihood": lik, "reconstruction-error": rec.view(B, 1)}
+        else:
+            elbo = E.elbo_combine(low_elbo if want_lik else None, logdet, rec, l1, pre, lw, self.regularization_param, mw,
+                                  B, dev)
+            out = {"elbo": elbo, "prior-dict": prior_dict}
+        if rerun is not None:
+            self._recompute_rows(out, x, rerun, want_lik, want_jac, add_rec, add_diag, add_off, lw, mw, ood, pre)
+        return out
+
+    def _recompute_rows(self, out, x, rows, want_lik, want_jac, add_rec, add_diag, add_off, lw, mw, ood, pre):
+        """The precision guard's re-run: evaluate rows ``rows`` (int64, device) of the sub-batch again under the guard's fallback
+        configuration and write them over ``out`` and ``self.last_gram`` (the fallback primal changes the encode too, so only a
+        whole re-run of the rows is consistent)."""
+        g = self.last_gram
+        sub = self._elbo_chunk(x.index_select(0, rows), want_lik, want_jac, add_rec, add_diag, add_off, lw, mw, ood,
+                               None if pre is None else pre.index_select(0, rows), kernels=self.precision_guard.fallback)
+        sg, self.last_gram = self.last_gram, g
+        _scatter_rows(out, rows, sub)
+        for k in ("jtj", "logdet", "l1_off", "l1_diag", "info", "cond"):
+            getattr(g, k).index_copy_(0, rows, getattr(sg, k))
 
     def _check_hutchinson_metric(self, offdiagonal):
         """The reference reshapes the off-diagonal entries of the (B, d, S) product to (B, d (d - 1)) (non_square.py:98): only
@@ -937,9 +1019,15 @@ class NonSquareHeadDensity(Density):
         raise ValueError(f"Unknown hutchinson distribution {self.hutchinson_distribution}")
 
     def _report_attempts(self, g):
+        """Sync mode: read the retry flags (and the precision guard's flag count, in the same copy), warn / raise like the
+        reference; returns the number of flagged samples (None without a guard estimate or in lazy mode)."""
         if self.check_cholesky != "sync":
-            return
-        fail = g.fail.tolist()                                   # one small D2H copy (synchronises the stream)
+            return None
+        if g.flagged_count is None:
+            fail = g.fail.tolist()                               # one small D2H copy (synchronises the stream)
+            flagged = None
+        else:
+            *fail, flagged = torch.cat((g.fail, g.flagged_count)).tolist()
         attempts = 1
         while attempts <= self.MAX_ATTEMPTS and fail[attempts - 1]:
             attempts += 1
@@ -949,6 +1037,7 @@ class NonSquareHeadDensity(Density):
         if attempts > 1:
             print(f"WARNING: Numerical non-invertibility in JtJ observed - {attempts} attempts needed to fix")
         g.attempts = attempts
+        return flagged
 
     # ------------------------------------------------------------------------------------------
     def _ood(self, x):

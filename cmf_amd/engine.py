@@ -719,7 +719,14 @@ def check_latent_width(d):
 
 
 class GramResult:
-    __slots__ = ("jtj", "logdet", "l1_off", "l1_diag", "info", "fail", "attempts")
+    """Outputs of ``gram_cholesky`` (all on the device).  ``gram_condition`` adds ``cond`` (B,) float32, ``flagged_count`` (1,)
+    int32 and ``flagged_idx`` (B,) int32; a guarded evaluation that re-ran rows on its fallback kernels lists them in
+    ``recomputed`` (int64).  Slots not filled are None."""
+    __slots__ = ("jtj", "logdet", "l1_off", "l1_diag", "info", "fail", "attempts", "cond", "flagged_idx", "flagged_count",
+                 "recomputed")
+
+    def __init__(self):
+        self.attempts = self.cond = self.flagged_idx = self.flagged_count = self.recomputed = None
 
 
 def gram_cholesky(T, d, max_attempts=6, eps0=1e-6):
@@ -759,6 +766,31 @@ def cholesky_retries(r, d, max_attempts=6, eps0=1e-6):
     for a in range(1, max_attempts):
         _lib.check(lib.cmf_cholesky_retry(_p(r.jtj), d, B, a, eps0, _p(r.logdet), _p(r.l1_diag), _p(r.info), _p(r.fail),
                                           _stream()), "cmf_cholesky_retry")
+
+
+def gram_condition(r, d, threshold):
+    """kappa_1 of every factorised Gram matrix in ``r`` (a GramResult of ``gram_cholesky``, after its retries) and the samples
+    above ``threshold``: fills ``r.cond`` (B,) float32 (+inf where the factorisation failed), ``r.flagged_idx`` (B,) int32
+    (ascending, -1 after the last) and ``r.flagged_count`` (1,) int32, all on the device, without synchronising."""
+    check_latent_width(d)
+    B, dev = r.jtj.shape[0], r.jtj.device
+    r.cond = torch.empty(B, dtype=torch.float32, device=dev)
+    r.flagged_idx = torch.empty(B, dtype=torch.int32, device=dev)
+    r.flagged_count = torch.empty(1, dtype=torch.int32, device=dev)
+    # 128 < d: the float64 factor lives in a torch-allocated workspace (a captured graph's pool serves it)
+    ws = torch.empty(2 * B * d * d, dtype=torch.float32, device=dev) if d > WIDE_NC else None
+    launch = lambda: _lib.check(_lib.load().cmf_gram_condition(_p(r.jtj), _p(r.info), d, B, float(threshold), _p(r.cond),
+                                                               _p(r.flagged_idx), _p(r.flagged_count), _p(ws), _stream()),
+                                "cmf_gram_condition")
+    TIMER = _timer()
+    if TIMER is None:
+        launch()
+    else:
+        # float64 multiply-adds: factorisation d^3/6, triangular inverse d^3/6, |G^-1| column sums d^3/3 (2 FLOP each); bytes:
+        # jtj in and cond out, plus for 128 < d the float64 matrix written once and re-read by every pass over it in L2 / HBM
+        wide = 8.0 * (d * d + 2 * d ** 3 / 3.0) if d > WIDE_NC else 0.0
+        TIMER.wrap("gram_condition", B * 2.0 * (2 * d ** 3 / 3.0), B * (4.0 * (d * d + 1) + wide) + 8.0 * B, launch)
+    return r
 
 
 def gram_backward(T, jtj, g_logdet=None, g_l1off=None, g_l1diag=None):

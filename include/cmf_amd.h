@@ -299,6 +299,18 @@ int cmf_gram_cholesky(const float* t, long long t_b, long long t_r, int n_rows, 
                       void* stream);
 int cmf_cholesky_retry(float* jtj, int d, int B, int attempt, float eps0, float* logdet, float* l1_diag,
                        int* info, int* fail, void* stream);
+/* Conditioning of the factorised Gram matrices (the precision guard of the no-grad log-density path):
+ *   cond[b] = kappa_1(G_b) = ||G_b||_1 ||G_b^-1||_1 of the matrix cmf_gram_cholesky / cmf_cholesky_retry left in jtj (the
+ *   jittered Gram whose log-det is reported), computed exactly in float64 (Cholesky, triangular inverse, |G^-1| column sums);
+ *   +inf when info[b] != 0, when the float64 factorisation meets a non-positive pivot, or when the value is not finite.
+ *   jtj is read (whole for ||G||_1, its lower triangle for the factorisation) and never written.
+ *   flagged_idx [B] int32: the samples with cond > threshold in ascending order (a prefix-sum compaction: independent of the order
+ *   in which workgroups finish), -1 after the last one;  flagged_count [1] int32: their number.  threshold may be +inf (nothing
+ *   flagged); NaN: CMF_EINVAL.
+ * Widths 1 <= d <= 512 (else CMF_EINVAL).  d <= 128 works in LDS and ignores ws (may be NULL); 128 < d needs a caller-owned
+ * workspace ws of 2 * B * d * d floats, 8-byte aligned (a float64 d x d matrix per sample).  No allocation, no synchronisation. */
+int cmf_gram_condition(const float* jtj, const int* info, int d, int B, float threshold, float* cond, int* flagged_idx,
+                       int* flagged_count, float* ws, void* stream);
 /* Reverse of the head above for training (autograd through non_square.py:307-308, :280-294, :87-100):
  *   dt(b, r, :) = 2 * t(b, r, :) * (g_logdet[b] * jtj_b^-1 + g_l1off[b] * sign(jtj_b)[i != j]
  *                                   + g_l1diag[b] * sign(jtj_b)[i == j])
