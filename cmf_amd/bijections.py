@@ -89,6 +89,43 @@ class Bijection(nn.Module):
     def _unwrap_tangent(T, shape):
         return T.to_dense(1)[:, :, 0].reshape(T.B, *shape).contiguous()
 
+    # FlowProgram's steps over the low-dimensional prior, for the layers that work in place (AffineCouplingBijection,
+    # AffineBijection): the tensor is returned, as by the out-of-place ``_PriorFlowLayer``s
+    def prior_encode(self, u, lj=None):                 # lj (B,) accumulates the log-jacobian
+        self.encode_(u, lj)
+        return u
+
+    def prior_decode(self, z):
+        self.decode_(z)
+        return z
+
+    def prior_encode_train(self, u, lj=None):
+        """``prior_encode`` keeping what ``prior_backward`` needs: returns (z, ctx)."""
+        return u, self.encode_train_(u, lj)
+
+    def prior_backward(self, dz, ctx, grads, dlj=None):
+        """Cotangent of the layer input from ``dz`` (B, d) and the cotangent ``dlj`` (B,) of the layer's log-jacobian;
+        parameter gradients accumulate into ``grads``."""
+        self.encode_backward_(dz, ctx, grads, dlj=dlj)
+        return dz
+
+
+class _CouplingCtx:
+    """What a coupling layer's decode step keeps for its adjoint or backward (``decode_ctx``), and its encode step for
+    ``encode_backward_`` (x, y, g, acts only).
+      x          the layer input (z before the in-place update)
+      y, g       the network's output and ScaledTanh derivative (one row of each for a zero-input layer, read with stride 0)
+      acts       the network's activations (None for a zero-input layer)
+      saved      the input tangent of every network layer (``engine.net_tangent(save=)``)
+      V, YT      the modified tangent rows before the update, the network's raw output tangent
+      zero_in    the network reads structural zeros only: no tangent network ran
+      recompute  (z, T), the layer's inputs, kept instead of all the rest under ``keep=False``"""
+    __slots__ = ("x", "y", "g", "acts", "saved", "V", "YT", "zero_in", "recompute")
+
+    def __init__(self, x=None, y=None, g=None, acts=None, zero_in=False, recompute=None):
+        self.x, self.y, self.g, self.acts, self.zero_in, self.recompute = x, y, g, acts, zero_in, recompute
+        self.saved = self.V = self.YT = None
+
 
 # --------------------------------------------------------------------------------------------------
 # affine coupling layers
@@ -135,9 +172,9 @@ class AffineCouplingBijection(Bijection):
         y, _, _ = E.net_primal(self.net, z, view, need_acts=False)
         E.acl_primal(z, y, self.maps(z.device), decode=False, lj=lj)
 
-    # Structural zeros (``zero_in=True``, decided by ``FlowProgram`` from the layer list alone, never from data): every element
-    # this layer's network reads is known to be zero for the primal AND for every tangent column -- the channels
-    # ``SplitDensity.pad_inputs`` appended (split.py:50-52) in front of a coupler whose pass-through half is exactly those
+    # Structural zeros (``zero_in=True``, decided by ``FlowProgram`` from the layer list alone, never from data; ResNet couplers
+    # only): every element this layer's network reads is known to be zero for the primal AND for every tangent column -- the
+    # channels ``SplitDensity.pad_inputs`` appended (split.py:50-52) in front of a coupler whose pass-through half is exactly those
     # (acl.py:148-160,169-189 with reverse_mask).  Then the network's tangent output is identically zero, so no tangent network
     # runs (x-dot_mod = e^{-s} v_mod, bit for bit what the full computation yields), and its primal output is the same for every
     # sample (one sample group, read with stride 0).  The reference burns the cycles; 1 coupler in 10 of the image models.
@@ -147,33 +184,46 @@ class AffineCouplingBijection(Bijection):
 
     def decode_(self, z, T=None, lj=None, ncols=None, zero_in=False, seed_columns=None):
         view = self.view(z.device)
-        if zero_in and self.net.kind == "resnet":
-            y, g = E.net_primal_zero_input(self.net, view, z.shape[0], z.device)
-            if T is not None:
-                E.acl_tangent(T, None, z, y, g, self.maps(z.device))
-            return E.acl_primal(z, y, self.maps(z.device), decode=True, lj=lj)
-        if ((T is None or (ncols is not None and ncols <= 15 and lj is None))
+        if (not zero_in and (T is None or (ncols is not None and ncols <= 15 and lj is None))
                 and E.mlp_coupler_supported(self.net, view, T, 2 * self.cmod)):
             return E.mlp_coupler(self.net, z, T, view, self.maps(z.device), decode=True, lj=lj, ncols=ncols)
         # the split-precision tangent pass reads relu' from bit masks written by the primal pass (engine.BitMask)
-        want = False if T is None else ("bits" if E.cfg().tangent == "bf16x3" else True)
-        y, g, acts = E.net_primal(self.net, z, view, need_acts=want)
-        if T is not None and seed_columns is not None:
+        c = self._primal(z, view, False if T is None else ("bits" if E.cfg().tangent == "bf16x3" else True), zero_in)
+        if T is not None:
+            self._tangent(T, c, view, seed_columns)
+        E.acl_primal(z, c.y, self.maps(z.device), decode=True, lj=lj)
+
+    def _primal(self, z, view, need_acts, zero_in=False, keep_input=False):
+        """Primal half of a decode step: the network on the layer input ``z`` (``need_acts``: what ``net_primal`` keeps), or the
+        cached output of a structurally zero input (no activations).  Returns the record; ``keep_input``: it holds a copy of z,
+        which the coupling update overwrites."""
+        x = z.clone() if keep_input else z
+        if zero_in:
+            y, g = E.net_primal_zero_input(self.net, view, z.shape[0], z.device)
+            return _CouplingCtx(x, y, g, None, zero_in=True)
+        return _CouplingCtx(x, *E.net_primal(self.net, z, view, need_acts=need_acts))
+
+    def _tangent(self, T, c, view, seed_columns=None, save=False):
+        """Tangent half on the primal record ``c``: pushes ``T`` through the layer in place.  It reads the layer input ``c.x``, so
+        it runs before the primal update.  ``save``: the state ``decode_backward`` reads (the modified tangent rows before the
+        update, the input tangent of every network layer, the network's raw output tangent) goes into ``c``."""
+        if save:
+            c.V = E.modified_rows(T, self.maps(c.x.device))
+            c.saved = None if c.zero_in else []
+        YT = None                                                    # zero_in: no network tangent at all
+        if seed_columns is None and not c.zero_in:
+            YT = E.net_tangent(self.net, T, view, c.acts, save=c.saved)
+        elif seed_columns is not None and seed_columns["n"] > 0:
             # first layer of the decode sweep (FlowProgram._seed_columns): T holds the tail's one-hot seeds, and only the columns
             # seeded at a pass-through element have a non-zero network tangent -- the network runs on those, packed
             sc = seed_columns
-            if sc["n"] == 0:                                         # no latent sits on a pass-through element: no network tangent at all
-                E.acl_tangent(T, None, z, y, g, self.maps(z.device))
-            else:
-                Tc = E.seed_tangent(T.B, T.N, sc["nc"], T.layout, sc["col_of"], sc["n"], z.device)
-                YTc = E.net_tangent(self.net, Tc, view, acts)
-                YT = E.expand_columns(YTc, T.nc, sc["colmap"])
-                YT.compact = getattr(YTc, "compact", False)
-                self._acl_tangent(T, YT, z, y, g)
-        elif T is not None:
-            YT = E.net_tangent(self.net, T, view, acts)
-            self._acl_tangent(T, YT, z, y, g)                       # uses z BEFORE the primal update
-        E.acl_primal(z, y, self.maps(z.device), decode=True, lj=lj)
+            Tc = E.seed_tangent(T.B, T.N, sc["nc"], T.layout, sc["col_of"], sc["n"], c.x.device)
+            YTc = E.net_tangent(self.net, Tc, view, c.acts)
+            YT = E.expand_columns(YTc, T.nc, sc["colmap"])
+            YT.compact = getattr(YTc, "compact", False)
+        if save:
+            c.YT = YT
+        self._acl_tangent(T, YT, c.x, c.y, c.g)
 
     def _acl_tangent(self, T, YT, z, y, g):
         if getattr(YT, "compact", False):
@@ -184,108 +234,94 @@ class AffineCouplingBijection(Bijection):
             return E.acl_tangent(T, YT, z, yc, gc, cm)
         E.acl_tangent(T, YT, z, y, g, self.maps(z.device))
 
-    # reverse sweep (J^T w): primal decode that keeps what the adjoint needs, then the adjoint step ------------
-    def decode_ctx_(self, z, zero_in=False):
-        view = self.view(z.device)
-        zb = z.clone()
-        if zero_in and self.net.kind == "resnet":
-            y, g = E.net_primal_zero_input(self.net, view, z.shape[0], z.device)
-            acts = "zero-input"
-        else:
-            y, g, acts = E.net_primal(self.net, z, view, need_acts=True)
-        E.acl_primal(z, y, self.maps(z.device), decode=True)
-        return zb, y, g, acts
+    # FlowProgram's steps (the interface every layer between head and tail answers) --------------------------------------
+    def encode(self, h):
+        self.encode_(h)                  # log-jac above the base is discarded: non_square.py:157-158,177
+        return h
 
-    def decode_vjp_(self, Ct, ctx):
-        """Adjoint of the tangent update of ``decode_`` on the cotangent stack ``Ct`` (in place)."""
-        zb, y, g, acts = ctx
-        dev = zb.device
-        if isinstance(acts, str):                          # zero_in: the rows the network reads are dropped by the split's adjoint
-            return E.acl_cotangent(Ct, None, zb, y, g, self.maps(dev))
-        YC = E.Tangent(Ct.B, y[0].numel(), Ct.nc, self.layout, dev)
-        YC.data.zero_()
-        E.acl_cotangent(Ct, YC, zb, y, g, self.maps(dev))
-        E.net_cotangent(self.net, YC, self.view(dev), acts, Ct)
+    def encode_nested(self, h, zeros):
+        lj = zeros()
+        self.encode_(h, lj)
+        return h, ("bijection", lj, h.clone())
 
-    # training (SURVEY 8 f1): decode keeping what the backward needs, and the backward of that step ------------
-    def decode_train_(self, z, T, keep=True, nc_hint=None, zero_in=False):
-        """``decode_`` on (z, T) in place; returns the context ``decode_backward_`` consumes: the layer input, the network's
-        outputs and activations and, with a tangent stack (``T`` not None), every layer's input tangent, the modified tangent
-        rows before the update and the network's raw tangent.  ``keep=False`` (recomputation): only the layer's inputs (z and a
-        copy of T: 1/17 of the hidden tangents of a ResNet coupler) are kept and the context is rebuilt in the backward pass.
-        ``zero_in``: no tangent network, nothing saved for one (the primal network still runs on the whole batch: its
-        per-sample activations are what the primal weight gradients are accumulated from)."""
-        zero_in = zero_in and self.net.kind == "resnet"
+    def encode_train(self, h):
+        return h, self.encode_train_(h)
+
+    def encode_backward(self, dh, ctx, grads):
+        self.encode_backward_(dh, ctx, grads)
+        return dh
+
+    def decode(self, z, T=None, ncols=None, zero_in=False, seed_columns=None):
+        self.decode_(z, T, ncols=ncols, zero_in=zero_in, seed_columns=seed_columns)
+        return z, T
+
+    def decode_ctx(self, z, T=None, zero_in=False, train=False, keep=True, nc_hint=None):
+        """``decode_`` on (z, T) in place; returns (z, T, the record ``decode_vjp`` / ``decode_backward`` read).  ``train``: the
+        activations ``net_primal_backward`` reads, and the primal network runs on the whole batch even under ``zero_in`` (the
+        primal weight gradients accumulate from its per-sample activations); ``nc_hint``: column slots of a later tangent sweep
+        over this primal-only pass.  ``keep=False`` (recomputation): only the layer's inputs (z and a copy of T: 1/17 of the
+        hidden tangents of a ResNet coupler) are kept, and ``decode_backward`` rebuilds the rest."""
         if not keep and T is not None and not zero_in:
-            ctx = ("recompute", z.clone(), E.Tangent(T.B, T.N, T.nc, T.layout, T.data.device, data=T.data[: T.B * T.N * T.nc].clone()))
+            c = _CouplingCtx(recompute=(z.clone(), E.Tangent(T.B, T.N, T.nc, T.layout, T.data.device,
+                                                             data=T.data[: T.B * T.N * T.nc].clone())))
             self.decode_(z, T)
-            return ctx
-        view, maps = self.view(z.device), self.maps(z.device)
-        zb = z.clone()
-        # ``nc_hint``: primal-only pass (T is None) whose activations a later tangent sweep with that many column slots reads
-        y, g, acts = E.net_primal(self.net, z, view, need_acts=E.train_acts_mode(self.net, view, z.shape[0], T, nc=nc_hint))
-        saved = V = YT = None
+            return z, T, c
+        view = self.view(z.device)
+        acts = E.train_acts_mode(self.net, view, z.shape[0], T, nc=nc_hint) if train else True
+        c = self._primal(z, view, acts, zero_in and not train, keep_input=True)
+        c.zero_in = zero_in
         if T is not None:
-            V = E.modified_rows(T, maps)
-            if zero_in:
-                saved = "zero-input"
-            else:
-                saved = []
-                YT = E.net_tangent(self.net, T, view, acts, save=saved)
-            E.acl_tangent(T, YT, z, y, g, maps)
-        E.acl_primal(z, y, maps, decode=True)
-        return zb, y, g, acts, saved, V, YT
+            self._tangent(T, c, view, save=True)
+        E.acl_primal(z, c.y, self.maps(z.device), decode=True)
+        return z, T, c
 
-    def decode_tangent_from_ctx_(self, ctx, T, save=False, zero_in=False):
-        """The tangent half of ``decode_train_`` on a context whose primal half is already there (``decode_train_(z, None)``):
-        pushes ``T`` through the layer in place.  ``save=False``: nothing is kept (the d-column sweep that only feeds the Gram
-        matrix); ``save=True``: returns the context ``decode_backward_`` consumes for THIS stack (the layer's primal state is
-        shared, not recomputed) -- the low-rank Hutchinson backward runs both on one primal decode."""
-        zb, y, g, acts = ctx[:4]
-        view, maps = self.view(zb.device), self.maps(zb.device)
-        V = E.modified_rows(T, maps) if save else None
-        if zero_in and self.net.kind == "resnet":
-            saved, YT = "zero-input", None
-        else:
-            saved = [] if save else None
-            YT = E.net_tangent(self.net, T, view, acts, save=saved)
-        self._acl_tangent(T, YT, zb, y, g)                   # zb: the layer input, i.e. z BEFORE the primal update
-        return (zb, y, g, acts, saved, V, YT) if save else None
+    def decode_tangent(self, T, ctx, save=False):
+        """The tangent half on the record of a primal-only ``decode_ctx``: pushes ``T`` through the layer in place and returns
+        (T, record of this stack for ``decode_backward`` -- sharing the primal state -- if ``save``, else None).  The low-rank
+        Hutchinson backward runs two stacks over one primal decode."""
+        c = _CouplingCtx(ctx.x, ctx.y, ctx.g, ctx.acts, ctx.zero_in) if save else ctx
+        self._tangent(T, c, self.view(c.x.device), save=save)
+        return T, (c if save else None)
 
-    def decode_backward_(self, Ct, dx, ctx, grads):
-        """Backward of ``decode_train_``: ``Ct`` (cotangent of the tangent stack, or None) and ``dx`` (cotangent of the primal
-        tensor) are updated in place from "after the layer" to "before the layer"; parameter gradients accumulate into ``grads``
-        (dict parameter -> tensor).  Order matters: the cross terms read the cotangent of the UPDATED tangent rows."""
-        if ctx[0] == "recompute":                          # rebuild this layer's state from its inputs (one more tangent sweep)
-            ctx = self.decode_train_(ctx[1], ctx[2], keep=True)
-        zb, y, g, acts, saved, V, YT = ctx
-        dev = zb.device
+    def decode_vjp(self, Ct, ctx, grads=None, cross=None):
+        """Adjoint of the tangent update of ``decode_`` on the cotangent stack ``Ct`` (in place; ``grads``, ``cross``: training)."""
+        c, dev = ctx, ctx.x.device
+        if c.zero_in:                                      # the rows the network reads are dropped by the split's adjoint
+            E.acl_cotangent(Ct, None, c.x, c.y, c.g, self.maps(dev))
+            return Ct
+        YC = E.Tangent(Ct.B, c.y[0].numel(), Ct.nc, self.layout, dev)
+        YC.data.zero_()
+        E.acl_cotangent(Ct, YC, c.x, c.y, c.g, self.maps(dev))
+        E.net_cotangent(self.net, YC, self.view(dev), c.acts, Ct, saved=c.saved, grads=grads, cross=cross)
+        return Ct
+
+    def decode_backward(self, Ct, dx, ctx, grads):
+        """Backward of ``decode_ctx``: ``Ct`` (cotangent of the tangent stack, or None) and ``dx`` (cotangent of the primal
+        tensor) are updated in place from "after the layer" to "before the layer" and returned; parameter gradients accumulate
+        into ``grads`` (dict parameter -> tensor).  Order matters: the cross terms read the cotangent of the UPDATED tangent rows."""
+        # recompute: rebuild this layer's state from its inputs (one more tangent sweep)
+        c = ctx if ctx.recompute is None else self.decode_ctx(*ctx.recompute, train=True)[2]
+        dev = c.x.device
         view, maps = self.view(dev), self.maps(dev)
-        dy = torch.zeros_like(y)
-        dg = None
-        zero_in = isinstance(saved, str)                   # no tangent network ran: s-dot = t-dot = 0 (decode_train_(zero_in=True))
-        if Ct is not None and zero_in:
-            # only the log-scale sees the tangent update (d/ds of e^{-s} v); no reverse sweep, no tangent weight gradients: the
-            # cotangent of the network's (zero) input tangent lands on rows the split's adjoint drops
-            dg = torch.zeros_like(g) if g is not None else None
-            E.acl_cross_terms(Ct, V, None, zb, y, g, maps, None, dy, dg)
-            E.acl_cotangent(Ct, None, zb, y, g, maps)
-        elif Ct is not None:
-            dg = torch.zeros_like(g) if g is not None else None
-            dz_ct = torch.zeros_like(zb)
-            E.acl_cross_terms(Ct, V, YT, zb, y, g, maps, dz_ct, dy, dg)
-            YC = E.Tangent(Ct.B, y[0].numel(), Ct.nc, self.layout, dev)
-            YC.data.zero_()
-            E.acl_cotangent(Ct, YC, zb, y, g, maps)
+        dy = torch.zeros_like(c.y)
+        dg = dz_ct = cross = None
+        if Ct is not None:
+            # zero_in: no tangent network ran (s-dot = t-dot = 0), only the log-scale sees the tangent update (d/ds of e^{-s} v);
+            # no reverse sweep, no tangent weight gradients: the cotangent of the network's (zero) input tangent lands on rows the
+            # split's adjoint drops
+            dg = torch.zeros_like(c.g) if c.g is not None else None
+            dz_ct = None if c.zero_in else torch.zeros_like(c.x)
+            E.acl_cross_terms(Ct, c.V, c.YT, c.x, c.y, c.g, maps, dz_ct, dy, dg)
             cross = {}
-            E.net_cotangent(self.net, YC, view, acts, Ct, saved=saved, grads=grads, cross=cross)
-        E.acl_primal_backward(dx, zb, y, maps, dy, decode=True)
-        if Ct is not None and not zero_in:
+            self.decode_vjp(Ct, c, grads=grads, cross=cross)
+        E.acl_primal_backward(dx, c.x, c.y, maps, dy, decode=True)
+        if dz_ct is not None:
             dx += dz_ct
         if self.net.kind == "resnet":
-            E.net_primal_backward(self.net, zb, view, acts, y, g, dy, dg, grads, dx)
+            E.net_primal_backward(self.net, c.x, view, c.acts, c.y, c.g, dy, dg, grads, dx)
         else:
-            E.mlp_primal_backward(self.net, zb, view, acts, dy, grads, dx, dh_extra=cross if Ct is not None else None)
+            E.mlp_primal_backward(self.net, c.x, view, c.acts, dy, grads, dx, dh_extra=cross)
+        return Ct, dx
 
     def encode_train_(self, z, lj=None):
         """``encode_`` keeping the layer input, the network output and its activations for ``encode_backward_``."""
@@ -293,19 +329,18 @@ class AffineCouplingBijection(Bijection):
         xb = z.clone()
         y, g, acts = E.net_primal(self.net, z, view, need_acts=E.train_acts_mode(self.net, view, z.shape[0]))
         E.acl_primal(z, y, self.maps(z.device), decode=False, lj=lj)
-        return xb, y, g, acts
+        return _CouplingCtx(xb, y, g, acts)
 
     def encode_backward_(self, dz, ctx, grads, dlj=None):
         """Backward of ``encode_train_`` in place on ``dz`` (cotangent of the layer output -> of its input); ``dlj`` (B,) is the
         cotangent of the layer's log-jacobian where it is used (the low-dimensional prior flows)."""
-        xb, y, g, acts = ctx
-        dev = xb.device
-        dy = torch.zeros_like(y)
-        E.acl_primal_backward(dz, xb, y, self.maps(dev), dy, decode=False, dlj=dlj)
+        c, dev = ctx, ctx.x.device
+        dy = torch.zeros_like(c.y)
+        E.acl_primal_backward(dz, c.x, c.y, self.maps(dev), dy, decode=False, dlj=dlj)
         if self.net.kind == "resnet":
-            E.net_primal_backward(self.net, xb, self.view(dev), acts, y, g, dy, None, grads, dz)
+            E.net_primal_backward(self.net, c.x, self.view(dev), c.acts, c.y, c.g, dy, None, grads, dz)
         else:
-            E.mlp_primal_backward(self.net, xb, self.view(dev), acts, dy, grads, dz)
+            E.mlp_primal_backward(self.net, c.x, self.view(dev), c.acts, dy, grads, dz)
 
     # protocol ------------------------------------------------------------------------------------
     def _x_to_z(self, x):
@@ -436,22 +471,54 @@ class _ReshapingBijection(Bijection):
         self._maps.put("z2x", self._reshape_z(idz).reshape(-1).numpy())    # x[r] = z[z2x[r]]
         self.n = n
 
+    # FlowProgram's steps (see AffineCouplingBijection; the coupler options ``**_`` do not apply, the contexts are None)
     def encode(self, x):
         return E.gather_primal(x, self._maps.get("x2z", x.device), self.n).view(x.shape[0], *self.z_shape)
 
-    def decode(self, z, T=None):
+    def encode_nested(self, h, zeros):
+        h = self.encode(h)
+        return h, ("bijection", zeros(), h.clone())
+
+    def encode_train(self, h):
+        return self.encode(h), None
+
+    def encode_backward(self, dh, ctx, grads):
+        return self.decode(dh)[0]                          # z[r] = x[x2z[r]]  ->  dx = dz[z2x]
+
+    def decode(self, z, T=None, **_):
         x = E.gather_primal(z, self._maps.get("z2x", z.device), self.n).view(z.shape[0], *self.x_shape)
         if T is not None:
             T = E.gather_tangent(T, self._maps.get("z2x", z.device), self.n)
         return x, T
 
-    def decode_tangent(self, T):
-        """``decode`` on a tangent stack alone (the primal tensor went through it in an earlier pass)."""
-        return E.gather_tangent(T, self._maps.get("z2x", T.data.device), self.n)
+    def decode_ctx(self, z, T=None, **_):
+        return (*self.decode(z, T), None)
 
-    def decode_vjp(self, Ct):
+    def decode_tangent(self, T, ctx=None, save=False):
+        """``decode`` on a tangent stack alone (the primal tensor went through it in an earlier pass): returns (T, None)."""
+        return E.gather_tangent(T, self._maps.get("z2x", T.data.device), self.n), None
+
+    def decode_vjp(self, Ct, ctx=None):
         """Adjoint of ``decode`` on a cotangent stack: the inverse index map."""
         return E.gather_tangent(Ct, self._maps.get("x2z", Ct.data.device), self.n)
+
+    def decode_backward(self, Ct, dx, ctx, grads):
+        if Ct is not None:
+            Ct = self.decode_vjp(Ct)
+        return Ct, self.encode(dx)                         # x[r] = z[z2x[r]]  ->  dz = dx[x2z]
+
+    # in the low-dimensional prior a reshaping layer computes nothing: FlowProgram's prior sweeps have always passed it by
+    def prior_encode(self, u, lj=None):
+        return u
+
+    def prior_decode(self, z):
+        return z
+
+    def prior_encode_train(self, u, lj=None):
+        return u, None
+
+    def prior_backward(self, dz, ctx, grads, dlj=None):
+        return dz
 
     def _zeros(self, t):
         return torch.zeros(t.shape[0], 1, dtype=t.dtype, device=t.device)
@@ -479,13 +546,13 @@ class ViewBijection(_ReshapingBijection):
     def encode(self, x):
         return x.view(x.shape[0], *self.z_shape)
 
-    def decode(self, z, T=None):
+    def decode(self, z, T=None, **_):
         return z.view(z.shape[0], *self.x_shape), T
 
-    def decode_tangent(self, T):
-        return T
+    def decode_tangent(self, T, ctx=None, save=False):
+        return T, None
 
-    def decode_vjp(self, Ct):
+    def decode_vjp(self, Ct, ctx=None):
         return Ct
 
 
@@ -522,21 +589,6 @@ class Squeeze2dBijection(_ReshapingBijection):
 class _PriorFlowLayer(Bijection):
     """A low-dimensional prior layer evaluated out of place: ``prior_encode(u, lj) -> z`` (lj (B,) accumulates the
     log-jacobian) and ``prior_decode(z) -> u`` as the reference's ``z_to_x`` computes it."""
-
-    def prior_encode(self, u, lj=None):
-        raise NotImplementedError
-
-    def prior_decode(self, z):
-        raise NotImplementedError
-
-    def prior_encode_train(self, u, lj=None):
-        """``prior_encode`` keeping what ``prior_backward`` needs: returns (z, ctx)."""
-        raise NotImplementedError
-
-    def prior_backward(self, dz, ctx, grads, dlj=None):
-        """Cotangent of the layer input from ``dz`` (B, d) and the cotangent ``dlj`` (B,) of the layer's log-jacobian;
-        parameter gradients accumulate into ``grads``."""
-        raise NotImplementedError
 
     def _x_to_z(self, x):
         E.require_gpu(x)

@@ -18,7 +18,7 @@ import torch
 import torch.nn as nn
 
 from . import engine as E
-from .bijections import AffineBijection, AffineCouplingBijection, _Elementwise, _PriorFlowLayer, _ReshapingBijection
+from .bijections import AffineBijection, AffineCouplingBijection, _CouplingCtx, _Elementwise, _PriorFlowLayer, _ReshapingBijection
 
 __all__ = ["Density", "BijectionDensity", "SplitDensity", "DiagonalGaussianDensity", "WrapperDensity",
            "DequantizationDensity", "DataParallelDensity", "NonSquareHeadDensity", "ManifoldFlowHeadDensity",
@@ -157,6 +157,53 @@ class SplitDensity(Density):
         if self.non_square:
             return self.pad_inputs(x1)["x"]
         return torch.cat((x1, self.density_2.sample(num_samples)), dim=self.dim)
+
+    # -- FlowProgram's steps (see AffineCouplingBijection): encode keeps the first channel half (split.py:16-17), decode
+    # zero-pads the dropped second half (split.py:50-52); the context is n, the elements of the half kept ---------------------
+    @staticmethod
+    def _index(n, device, start=0, pad=False):
+        """int32 gather index of elements start .. start + n - 1, then (``pad``) n zeros.  Built per call: a cached index would
+        change what a captured graph holds."""
+        idx = torch.arange(start, start + n, dtype=torch.int32, device=device)
+        return torch.cat((idx, torch.full((n,), -1, dtype=torch.int32, device=device))) if pad else idx
+
+    def encode(self, h, half=0):                         # half=1: the dropped half (encode_nested's level)
+        B, n = h.shape[0], h[0].numel() // 2
+        return E.gather_primal(h, self._index(n, h.device, start=half * n), n).view(B, h.shape[1] // 2, *h.shape[2:])
+
+    def encode_nested(self, h, zeros):
+        h2 = self.encode(h, half=1)
+        lp2 = zeros()
+        self.density_2.logprob_accumulate(h2, lp2)
+        return self.encode(h), ("split", lp2, h2)
+
+    def encode_train(self, h):
+        return self.encode(h), h[0].numel() // 2
+
+    def encode_backward(self, dh, n, grads):
+        return self.decode(dh)[0]                          # the dropped half gets no gradient
+
+    def decode(self, z, T=None, **_):
+        B, n = z.shape[0], z[0].numel()
+        idx = self._index(n, z.device, pad=True)
+        z = E.gather_primal(z, idx, 2 * n).view(B, 2 * z.shape[1], *z.shape[2:])
+        return z, (None if T is None else E.gather_tangent(T, idx, 2 * n))
+
+    def decode_ctx(self, z, T=None, **_):
+        n = z[0].numel()
+        return (*self.decode(z, T), n)
+
+    def decode_tangent(self, T, n, save=False):
+        return E.gather_tangent(T, self._index(n, T.data.device, pad=True), 2 * n), n
+
+    def decode_vjp(self, Ct, n):                          # adjoint of the zero-padding: keep the first half
+        return E.gather_tangent(Ct, self._index(n, Ct.data.device), n)
+
+    def decode_backward(self, Ct, dx, n, grads):
+        if Ct is not None:
+            Ct = self.decode_vjp(Ct, n)
+        B = dx.shape[0]
+        return Ct, dx.reshape(B, -1)[:, :n].reshape(B, dx.shape[1] // 2, *dx.shape[2:]).contiguous()
 
 
 class DiagonalGaussianDensity(Density):
@@ -472,22 +519,12 @@ class FlowProgram:
         B = x.shape[0]
         h = x.detach().clone().contiguous()
         for m in self.layers:
-            if isinstance(m, AffineCouplingBijection):
-                m.encode_(h)                     # log-jac above the base is discarded: non_square.py:157-158,177
-            elif isinstance(m, SplitDensity):
-                n = h[0].numel() // 2            # keep channel half 1 (split.py:16-17)
-                idx = torch.arange(n, dtype=torch.int32, device=h.device)
-                h = E.gather_primal(h, idx, n).view(B, h.shape[1] // 2, *h.shape[2:])
-            else:
-                h = m.encode(h)
+            h = m.encode(h)
         z_low = E.gather_primal(h, self.tail.gather_index(h.device), self.d)
         u = z_low.clone()
         lj = torch.zeros(B, dtype=torch.float32, device=x.device)
         for m in self.prior:
-            if isinstance(m, (AffineCouplingBijection, AffineBijection)):
-                m.encode_(u, lj)
-            elif isinstance(m, _PriorFlowLayer):             # nsf prior layers: out of place
-                u = m.prior_encode(u, lj)
+            u = m.prior_encode(u, lj)
         self.gaussian.logprob_accumulate(u, lj)
         return z_low, lj, u
 
@@ -504,30 +541,14 @@ class FlowProgram:
         h = x.detach().clone().contiguous()
         levels = []                                  # (kind, contribution to the elbo (B,), payload)
         for m in self.layers:
-            if isinstance(m, AffineCouplingBijection):
-                lj = zeros()
-                m.encode_(h, lj)
-                levels.append(("bijection", lj, h.clone()))
-            elif isinstance(m, SplitDensity):
-                n = h[0].numel() // 2
-                h2 = E.gather_primal(h, torch.arange(n, 2 * n, dtype=torch.int32, device=dev), n)
-                h2 = h2.view(B, h.shape[1] // 2, *h.shape[2:])
-                lp2 = zeros()
-                m.density_2.logprob_accumulate(h2, lp2)
-                h = E.gather_primal(h, torch.arange(n, dtype=torch.int32, device=dev), n).view(B, h.shape[1] // 2, *h.shape[2:])
-                levels.append(("split", lp2, h2))
-            else:
-                h = m.encode(h)
-                levels.append(("bijection", zeros(), h.clone()))
+            h, level = m.encode_nested(h, zeros)
+            levels.append(level)
         z_low = E.gather_primal(h, self.tail.gather_index(dev), self.d)
         levels.append(("tail", zeros(), z_low))
         u = z_low.clone()
         for m in self.prior:
             lj = zeros()
-            if isinstance(m, (AffineCouplingBijection, AffineBijection)):
-                m.encode_(u, lj)
-            elif isinstance(m, _PriorFlowLayer):
-                u = m.prior_encode(u, lj)
+            u = m.prior_encode(u, lj)
             levels.append(("bijection", lj, u.clone()))
         lp = zeros()
         self.gaussian.logprob_accumulate(u, lp)
@@ -544,8 +565,11 @@ class FlowProgram:
                 node = {"elbo": acc.view(B, 1), "low-dim-x": payload, "prior-dict": node}
         return z_low, low_elbo, u, node
 
-    def _decode_order(self):
-        return [(i, self.layers[i]) for i in reversed(range(len(self.layers)))]
+    def _decode_steps(self, seed=None):
+        """The layers in decode order (the list backwards) as (layer, zero_in, seed_columns): the structural-zero flag of each
+        (``_structural_zeros``) and ``seed``, a ``_seed_columns`` plan, on the layer it names (None elsewhere)."""
+        for i in reversed(range(len(self.layers))):
+            yield self.layers[i], self._zero(i), (seed if seed is not None and seed["index"] == i else None)
 
     # -- z_low -> (x_hat, J) ----------------------------------------------------------------------
     @_scoped
@@ -554,24 +578,13 @@ class FlowProgram:
         N = int(np.prod(self.tail.x_shape))
         scatter = self.tail.scatter_index(dev)
         z = E.gather_primal(z_low.contiguous(), scatter, N).view(B, *self.tail.x_shape)
-        T, ncols = None, None
-        seed = None
+        T = ncols = seed = None
         if tangents:
             ncols = self.d if eps is None else eps.shape[2]
             T = E.seed_tangent(B, N, E.ceil16(ncols), self.layout, scatter, self.d, dev, eps=eps)
             seed = self._seed_columns(dev) if eps is None else None      # (probe directions are dense: every column is live)
-        for i, m in self._decode_order():
-            if isinstance(m, AffineCouplingBijection):
-                m.decode_(z, T, ncols=ncols, zero_in=self._zero(i), seed_columns=seed if seed is not None and seed["index"] == i else None)
-            elif isinstance(m, SplitDensity):
-                n = z[0].numel()                 # zero-pad the dropped half (split.py:50-52)
-                idx = torch.cat((torch.arange(n, dtype=torch.int32, device=dev),
-                                 torch.full((n,), -1, dtype=torch.int32, device=dev)))
-                z = E.gather_primal(z, idx, 2 * n).view(B, 2 * z.shape[1], *z.shape[2:])
-                if T is not None:
-                    T = E.gather_tangent(T, idx, 2 * n)
-            else:
-                z, T = m.decode(z, T)
+        for m, zero_in, seed_columns in self._decode_steps(seed):
+            z, T = m.decode(z, T, ncols=ncols, zero_in=zero_in, seed_columns=seed_columns)
         return z, T
 
     # -- reverse sweep: cotangents in data space -> J^T w in latent space ---------------------------
@@ -581,32 +594,16 @@ class FlowProgram:
         (B, d, S) -- the vjp of ``flow_forward`` (non_square.py:190-201) for S directions at once.  A primal decode keeps
         each coupling layer's state, then the layers' adjoints run in encode order; transposed convolutions use the fp32
         MFMA kernel (``engine.net_cotangent``)."""
-        B, dev = z_low.shape[0], z_low.device
-        N = int(np.prod(self.tail.x_shape))
-        z = E.gather_primal(z_low.contiguous(), self.tail.scatter_index(dev), N).view(B, *self.tail.x_shape)
+        z = self.tail.low_dim_to_masked(z_low)["x"]
         ctx = []
-        for i, m in self._decode_order():
-            if isinstance(m, AffineCouplingBijection):
-                ctx.append(m.decode_ctx_(z, zero_in=self._zero(i)))
-            elif isinstance(m, SplitDensity):
-                n = z[0].numel()
-                idx = torch.cat((torch.arange(n, dtype=torch.int32, device=dev),
-                                 torch.full((n,), -1, dtype=torch.int32, device=dev)))
-                z = E.gather_primal(z, idx, 2 * n).view(B, 2 * z.shape[1], *z.shape[2:])
-                ctx.append(n)
-            else:
-                z, _ = m.decode(z, None)
-                ctx.append(None)
+        for m, zero_in, _ in self._decode_steps():
+            z, _, c = m.decode_ctx(z, zero_in=zero_in)
+            ctx.append(c)
         S = Wd.shape[2]
         Ct = E.Tangent.from_dense(Wd.contiguous().float(), E.ceil16(S), self.layout)
         for m, c in zip(self.layers, reversed(ctx)):
-            if isinstance(m, AffineCouplingBijection):
-                m.decode_vjp_(Ct, c)
-            elif isinstance(m, SplitDensity):                      # adjoint of the zero-padding: keep the first half
-                Ct = E.gather_tangent(Ct, torch.arange(c, dtype=torch.int32, device=dev), c)
-            else:
-                Ct = m.decode_vjp(Ct)
-        out = E.gather_tangent(Ct, self.tail.gather_index(dev), self.d)
+            Ct = m.decode_vjp(Ct, c)
+        out = E.gather_tangent(Ct, self.tail.gather_index(z_low.device), self.d)
         return z, out.to_dense(S).contiguous()
 
     # -- training: decode with saved state, and its backward (SURVEY 8 f1) -------------------------------
@@ -624,19 +621,9 @@ class FlowProgram:
         assert nc % 16 == 0 and nc >= ncols
         T = E.seed_tangent(B, N, nc, self.layout, scatter, self.d, dev, eps=eps) if tangents else None
         ctx = []
-        for i, m in self._decode_order():
-            if isinstance(m, AffineCouplingBijection):
-                ctx.append(m.decode_train_(z, T, keep, nc_hint=nc_hint, zero_in=self._zero(i)))
-            elif isinstance(m, SplitDensity):
-                n = z[0].numel()
-                idx = torch.cat((torch.arange(n, dtype=torch.int32, device=dev),
-                                 torch.full((n,), -1, dtype=torch.int32, device=dev)))
-                z = E.gather_primal(z, idx, 2 * n).view(B, 2 * z.shape[1], *z.shape[2:])
-                T = E.gather_tangent(T, idx, 2 * n) if T is not None else None
-                ctx.append(n)
-            else:
-                z, T = m.decode(z, T)
-                ctx.append(None)
+        for m, zero_in, _ in self._decode_steps():
+            z, T, c = m.decode_ctx(z, T, zero_in=zero_in, train=True, keep=keep, nc_hint=nc_hint)
+            ctx.append(c)
         return z, T, ctx
 
     @_scoped
@@ -644,23 +631,15 @@ class FlowProgram:
         """A tangent sweep over the PRIMAL contexts of ``decode_train(z_low, tangents=False)``: returns (T, ctx') where ctx' is
         the context list ``decode_backward`` consumes when ``save`` (else None).  Layers are walked like ``decode_train``."""
         dev = self.tail.permutation.device
-        B = next(c[0].shape[0] for c in ctx if isinstance(c, tuple))
+        B = next(c.x.shape[0] for c in ctx if isinstance(c, _CouplingCtx))
         N = int(np.prod(self.tail.x_shape))
         ncols = self.d if eps is None else eps.shape[2]
         nc = E.ceil16(ncols) if nc is None else int(nc)
         T = E.seed_tangent(B, N, nc, self.layout, self.tail.scatter_index(dev), self.d, dev, eps=eps)
         out = []
-        for (i, m), c in zip(self._decode_order(), ctx):
-            if isinstance(m, AffineCouplingBijection):
-                out.append(m.decode_tangent_from_ctx_(c, T, save, zero_in=self._zero(i)))
-            elif isinstance(m, SplitDensity):
-                n = c
-                idx = torch.cat((torch.arange(n, dtype=torch.int32, device=dev), torch.full((n,), -1, dtype=torch.int32, device=dev)))
-                T = E.gather_tangent(T, idx, 2 * n)
-                out.append(n)
-            else:
-                T = m.decode_tangent(T)
-                out.append(None)
+        for m, c in zip(reversed(self.layers), ctx):
+            T, c = m.decode_tangent(T, c, save)
+            out.append(c)
         return T, (out if save else None)
 
     @_scoped
@@ -670,16 +649,7 @@ class FlowProgram:
         B, dev = dx.shape[0], dx.device
         dx = dx.detach().clone().contiguous()
         for m, c in zip(self.layers, reversed(ctx)):
-            if isinstance(m, AffineCouplingBijection):
-                m.decode_backward_(Ct, dx, c, grads)
-            elif isinstance(m, SplitDensity):                      # adjoint of the zero-padding: keep the first half
-                if Ct is not None:
-                    Ct = E.gather_tangent(Ct, torch.arange(c, dtype=torch.int32, device=dev), c)
-                dx = dx.reshape(B, -1)[:, :c].reshape(B, dx.shape[1] // 2, *dx.shape[2:]).contiguous()
-            else:
-                if Ct is not None:
-                    Ct = m.decode_vjp(Ct)
-                dx = m.encode(dx)                                  # x[r] = z[z2x[r]]  ->  dz = dx[x2z]
+            Ct, dx = m.decode_backward(Ct, dx, c, grads)
         return E.gather_primal(dx.reshape(B, -1), self.tail.gather_index(dev), self.d)
 
     @_scoped
@@ -689,26 +659,15 @@ class FlowProgram:
         h = x.detach().clone().contiguous()
         ctx = []
         for m in self.layers:
-            if isinstance(m, AffineCouplingBijection):
-                ctx.append(m.encode_train_(h))
-            elif isinstance(m, SplitDensity):
-                n = h[0].numel() // 2
-                idx = torch.arange(n, dtype=torch.int32, device=h.device)
-                h = E.gather_primal(h, idx, n).view(B, h.shape[1] // 2, *h.shape[2:])
-                ctx.append(n)
-            else:
-                h = m.encode(h)
-                ctx.append(None)
+            h, c = m.encode_train(h)
+            ctx.append(c)
         z_low = E.gather_primal(h, self.tail.gather_index(h.device), self.d)
         u = z_low.clone()
         lj = torch.zeros(B, dtype=torch.float32, device=x.device)
         pctx = []
         for m in self.prior:
-            if isinstance(m, _PriorFlowLayer):                     # nsf prior layers: out of place
-                u, c = m.prior_encode_train(u, lj)
-                pctx.append((m, c))
-            elif isinstance(m, (AffineCouplingBijection, AffineBijection)):
-                pctx.append((m, m.encode_train_(u, lj)))
+            u, c = m.prior_encode_train(u, lj)
+            pctx.append(c)
         if self.gaussian._nonstandard():
             raise NotImplementedError("training gradients with a non-standard base Gaussian are not built")
         self.gaussian.logprob_accumulate(u, lj)
@@ -722,27 +681,16 @@ class FlowProgram:
         dlow = dlow.to(torch.float32).contiguous()
         E._lib.check(E._lib.load().cmf_gaussian_backward(E._p(u.contiguous()), E._p(dlow), u.shape[1], u.shape[0], E._p(du),
                                                          E._stream()), "cmf_gaussian_backward")
-        for m, c in reversed(pctx):
-            if isinstance(m, _PriorFlowLayer):
-                du = m.prior_backward(du, c, grads, dlj=dlow)
-            else:
-                m.encode_backward_(du, c, grads, dlj=dlow)
+        for m, c in zip(reversed(self.prior), reversed(pctx)):
+            du = m.prior_backward(du, c, grads, dlj=dlow)
         return du
 
     @_scoped
     def encode_backward(self, ctx, dz_low, grads):
         """Backward of the encode chain above the base: cotangent of z_low -> parameter gradients (and the unused cotangent of x)."""
-        B, dev = dz_low.shape[0], dz_low.device
-        N = int(np.prod(self.tail.x_shape))
-        dh = E.gather_primal(dz_low.contiguous(), self.tail.scatter_index(dev), N).view(B, *self.tail.x_shape)
+        dh = self.tail.low_dim_to_masked(dz_low)["x"]
         for m, c in zip(reversed(self.layers), reversed(ctx)):
-            if isinstance(m, AffineCouplingBijection):
-                m.encode_backward_(dh, c, grads)
-            elif isinstance(m, SplitDensity):                      # the dropped half gets no gradient
-                idx = torch.cat((torch.arange(c, dtype=torch.int32, device=dev), torch.full((c,), -1, dtype=torch.int32, device=dev)))
-                dh = E.gather_primal(dh, idx, 2 * c).view(B, 2 * dh.shape[1], *dh.shape[2:])
-            else:
-                dh = m.decode(dh, None)[0]                         # z[r] = x[x2z[r]]  ->  dx = dz[z2x]
+            dh = m.encode_backward(dh, c, grads)
         return dh
 
     # -- latent noise -> z_low (sampling) ----------------------------------------------------------
@@ -750,10 +698,7 @@ class FlowProgram:
     def prior_inverse(self, u):
         z = u.detach().clone().contiguous()
         for m in reversed(self.prior):
-            if isinstance(m, (AffineCouplingBijection, AffineBijection)):
-                m.decode_(z)
-            elif isinstance(m, _PriorFlowLayer):
-                z = m.prior_decode(z)
+            z = m.prior_decode(z)
         return z
 
 

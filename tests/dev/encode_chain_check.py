@@ -8,7 +8,6 @@ from test_gpu_parity import build, find_head
 from oracle import cmf_oracle as O
 from cmf_amd import engine as E
 from cmf_amd.bijections import AffineCouplingBijection
-from cmf_amd.densities import SplitDensity
 name = sys.argv[1] if len(sys.argv) > 1 else "c3_mnist_full"
 g, meta, cfg, dens = build(name)
 _, schema, x_shape, ops, sd = golden_model(meta, dtype=torch.float64)
@@ -49,13 +48,7 @@ print(f"after tail: {err(dh, hs[-1].grad):.1e}")
 grads = {}
 i = len(hs) - 1
 for m, c in zip(reversed(prog.layers), reversed(ctx)):
-    if isinstance(m, AffineCouplingBijection):
-        m.encode_backward_(dh, c, grads)
-    elif isinstance(m, SplitDensity):
-        idx = torch.cat((torch.arange(c, dtype=torch.int32, device=dev), torch.full((c,), -1, dtype=torch.int32, device=dev)))
-        dh = E.gather_primal(dh, idx, 2 * c).view(B, 2 * dh.shape[1], *dh.shape[2:])
-    else:
-        dh = m.decode(dh, None)[0]
+    dh = m.encode_backward(dh, c, grads)
     i -= 1
     print(f"after {type(m).__name__[:24]:24s} -> cotangent of input {tuple(dh.shape[1:])}: err {err(dh, hs[i].grad):.1e}", flush=True)
 
@@ -69,10 +62,10 @@ print(f"first step, FRESH ctx from the oracle's layer input: err {err(d1, hs[-2]
 chain_ctx = ctx[-1]
 d2 = dh0.clone(); last.encode_backward_(d2, chain_ctx, {})
 print(f"first step, ctx kept by encode_train:               err {err(d2, hs[-2].grad):.1e}")
-names = ["xb", "y", "g"]
-for nm, a, b in zip(names, fresh[:3], chain_ctx[:3]):
+for nm in ("x", "y", "g"):
+    a, b = getattr(fresh, nm), getattr(chain_ctx, nm)
     print(f"   {nm}: fresh vs chain max abs diff {float((a - b).abs().max()):.2e} (max |.| {float(a.abs().max()):.2e})")
-for i, (a, b) in enumerate(zip(fresh[3], chain_ctx[3])):
+for i, (a, b) in enumerate(zip(fresh.acts, chain_ctx.acts)):
     flips = int(((a > 0) != (b > 0)).sum())
-    if flips or i in (0, len(fresh[3]) - 1):
+    if flips or i in (0, len(fresh.acts) - 1):
         print(f"   act {i}: max abs diff {float((a - b).abs().max()):.2e}, relu sign flips {flips} of {a.numel()}")

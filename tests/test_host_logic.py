@@ -292,9 +292,8 @@ def test_structural_zero_plan_matches_the_oracles_data(name):
                 h, hv = O.squeeze_z_to_x(h, op["factor"]), O.squeeze_z_to_x(hv, op["factor"])
             elif op["kind"] == "split":
                 h, hv = torch.cat((h, torch.zeros_like(h)), 1), torch.cat((hv, torch.zeros_like(hv)), 2)
-    order = [i for i, _ in prog._decode_order()]
-    acl_pos = {i: n for n, i in enumerate(i for i in order if isinstance(prog.layers[i], AffineCouplingBijection))}
-    assert sorted(acl_pos[i] for i in prog.zero_in) == zero_ops
+    flags = [zero_in for m, zero_in, _ in prog._decode_steps() if isinstance(m, AffineCouplingBijection)]
+    assert [k for k, zero_in in enumerate(flags) if zero_in] == zero_ops
     if name.startswith("mini"):                               # image schemas (schemas.py:399-412): exactly one, right behind the pad
         (i,) = prog.zero_in
         assert isinstance(prog.layers[i], SplitChannelwiseAffineCouplingBijection) and prog.layers[i].reverse_mask
