@@ -481,6 +481,7 @@ extern "C" int cmf_conv_tangent(const cmf_conv_tangent_args* ap, void* stream) {
   if (a.fo && (a.fomode < CMF_F_RELU || a.fomode > CMF_F_SELF_RELU)) return CMF_EINVAL;
   if (a.fo && a.fomode == CMF_F_SELF_RELU && ((a.fo_np | a.fo_co | a.fo_px) % 4 || (uintptr_t)a.fo % 16)) return CMF_EINVAL;
   if (a.mask_out && (a.cout % 16 || a.mask_np < (long long)a.H * a.W * (a.cout / 8))) return CMF_EINVAL;
+  if (a.ymask) return CMF_EINVAL;                               // the store filter is cmf_conv_tangent_bf16x3's
   const long long HW = (long long)a.H * a.W;
   // per-sample offsets are held in 32-bit registers
   if (!fits_int((a.cin + 8) * a.x_ci + HW * a.x_px + a.nc) || !fits_int((a.cin + 8) * a.f_ci + HW * a.f_px) ||

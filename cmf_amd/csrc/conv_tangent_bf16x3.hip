@@ -21,6 +21,9 @@
 //             cmf_pack_weight_bf16x3, so staging is a straight copy.
 // A staging thread owns one (pixel, 4 columns) item: it loads the 8 channels of the octet (8 x 16 B),
 // applies the activation-derivative factor, splits, and writes 4 + 4 ds_write_b128.
+// relu-dead rows (CMF_F_RELU_BITS): a (channel, pixel) row of a slice -- one aligned 64-byte segment, four neighbouring loader
+// lanes -- whose mask bit is clear is NOT FETCHED (loader waves: per-load offsets, out of the descriptor's range when dead), and
+// a launch with a store filter (a.ymask, MODE 6 / 7) does not WRITE the rows its output's only reader will not fetch.
 #include <cstdlib>
 #include <type_traits>
 #include "common.h"
@@ -179,7 +182,10 @@ __global__ __launch_bounds__(512, 2) void conv_tangent_bf16x3_kernel(cmf_conv_ta
   // MODE: 0 = general factor formula, 1 = relu factor (2 instead of 6 VALU per channel in the loader), 2 = SELF (the
   // input's own relu, no factor stream).  Compile-time: every loader VALU instruction delays the MFMA wave it shares
   // a SIMD with.
-  constexpr bool SELF = MODE == 2, RELU = MODE == 1, BITS = MODE == 3;   // 3 = relu' from a bit mask (CMF_F_RELU_BITS)
+  // 6 / 7 = RELU / BITS with an OUTPUT row filter (a.ymask: rows the output's only reader will not fetch are not stored; below)
+  constexpr bool YMASK = !F16 && (MODE == 6 || MODE == 7);
+  static_assert(!YMASK || (COT == 4 && !CKB), "the store filter: whole 64-channel groups, every pixel");
+  constexpr bool SELF = MODE == 2, RELU = MODE == 1 || MODE == 6, BITS = MODE == 3 || MODE == 7;   // 3 = relu' from a bit mask (CMF_F_RELU_BITS)
   // 4 = PLAIN: no input factor at all (no factor stream, like SELF, and no relu) and an optional OUTPUT-side relu' bit mask
   // applied at the store -- the reverse (cotangent) sweep: the adjoint of "mask, then conv" is "transposed conv, then mask"
   constexpr bool PLAIN = !F16 && (MODE == 4 || MODE == 5);
@@ -287,13 +293,19 @@ __global__ __launch_bounds__(512, 2) void conv_tangent_bf16x3_kernel(cmf_conv_ta
     // so when commit(g+1) starts the loads issued after X,f(g+1) are W(g), X,f(g+2), W(g+1), X,f(g+3), and after
     // W(g+1) only X,f(g+3).  To keep those counts constant the stream is padded: past the last chunk the cursors stay
     // on the last chunk (re-fetching it, ~3 chunks per workgroup and launch) instead of skipping loads.
+    // BITS: the "f" of a group is ONE byte load and it is the mask byte of the chunk three prefetches later (below); a dropped X
+    // load is still a load in this count.
     typedef int i32x4 __attribute__((ext_vector_type(4)));
-    auto make_rsrc = [&](const void* p) {
+    // BITS: the x and mask descriptors carry a finite record count, like the y descriptor of the MFMA waves: every real per-lane
+    // offset (below 2^29, launcher) passes the range check, X_DROP does not -- such a load fetches nothing, returns 0 and is still
+    // counted by vmcnt.  The scalar offset (the channel term) is not part of a raw buffer's range check.
+    constexpr int X_RECORDS = BITS ? 0x7fffff00 : -1, X_DROP = 0x7ffffff0;
+    auto make_rsrc = [&](const void* p, int records = -1) {
       const unsigned long long u = reinterpret_cast<unsigned long long>(p);
       i32x4 d;
       d[0] = __builtin_amdgcn_readfirstlane((int)(unsigned)u);
       d[1] = __builtin_amdgcn_readfirstlane((int)((unsigned)(u >> 32) & 0xffffu));      // stride 0
-      d[2] = -1;                                                                          // no range check
+      d[2] = records;                                                                     // -1: no range check
       d[3] = 0x00020000;
       return d;
     };
@@ -301,19 +313,37 @@ __global__ __launch_bounds__(512, 2) void conv_tangent_bf16x3_kernel(cmf_conv_ta
     i32x4 xrs = make_rsrc(a.x), frs = xrs, wrs = make_rsrc(a.w);
     int xo = 0, fo = 0;
     float okf = 0.f;
+    // BITS: a relu-dead (channel, pixel) row of x is NOT FETCHED.  Each of a chunk's eight X loads gets its own per-lane offset:
+    // xo where the pixel's mask byte has the channel's bit set, X_DROP otherwise -- the registers then hold x or an exact 0 and
+    // commit neither extracts bits nor multiplies.  A halo pixel outside the image (or an idle loader thread) reads its mask
+    // byte at X_DROP: the byte is 0 and all eight rows are dropped.  The byte must have LANDED before the X loads of its chunk
+    // are issued, so the byte stream runs three prefetches ahead of the X stream with a cursor of its own (mcur_*, mo): the
+    // byte loaded behind the X loads of chunk g is chunk g + 3's, i.e. the next chunk of the SAME register set.  It is the last
+    // load of chunk g's group, so the wait_x(g) of iteration g - 1 covers it, and iteration g's prefetch of chunk g + 3 reads
+    // it: no wait is added, the load stream keeps its shape (8 X, 1 byte, NW weight loads per iteration) and every vmcnt
+    // immediate below stays what it was.  Both cursors pad the stream the same way, so set g % 3 always holds chunk g's byte.
+    [[maybe_unused]] int mcur_item = 0, mcur_ch = 0, mo = 0;
+    [[maybe_unused]] auto mset_item = [&](int item) {
+      int tile, slice, cog, np;
+      decode(item, tile, slice, cog, np);
+      const int y0 = C::TH * (tile / tiles_x), x0 = C::TW * (tile % tiles_x);
+      frs = make_rsrc(reinterpret_cast<const unsigned char*>(a.f) + (long long)np * a.f_np, X_RECORDS);       // f_np in bytes
+      const int gy = y0 - 1 + hy, gx = x0 - 1 + hx;
+      const bool ok = lt < C::NX_ITEMS && gy >= 0 && gy < a.H && gx >= 0 && gx < a.W;
+      mo = ok ? (gy * a.W + gx) * (a.cin / 8) : X_DROP;
+    };
     auto set_item = [&](int item) {
       int tile, slice, cog, np;
       decode(item, tile, slice, cog, np);
       const int y0 = C::TH * (tile / tiles_x), x0 = C::TW * (tile % tiles_x);
-      xrs = make_rsrc(a.x + (long long)np * a.x_np + (long long)slice * (a.x_sl ? a.x_sl : 16));
-      frs = BITS ? make_rsrc(reinterpret_cast<const unsigned char*>(a.f) + (long long)np * a.f_np)        // f_np in bytes
-                 : make_rsrc(a.f ? a.f + (long long)(np / fgrp) * a.f_np + (np % fgrp) : a.x);
+      xrs = make_rsrc(a.x + (long long)np * a.x_np + (long long)slice * (a.x_sl ? a.x_sl : 16), X_RECORDS);
+      if constexpr (!BITS) frs = make_rsrc(a.f ? a.f + (long long)(np / fgrp) * a.f_np + (np % fgrp) : a.x);
       const int gy = y0 - 1 + hy, gx = x0 - 1 + hx;
       const bool ok = lt < C::NX_ITEMS && gy >= 0 && gy < a.H && gx >= 0 && gx < a.W;
       const int gpix = gy * a.W + gx;
       okf = ok ? 1.f : 0.f;
       xo = ok ? 4 * (gpix * x_px + q * 4) : 0;
-      fo = ok ? (BITS ? gpix * (a.cin / 8) : 4 * (gpix * f_px)) : 0;
+      fo = ok ? 4 * (gpix * f_px) : 0;                             // (BITS: the mask stream has its own cursor, mset_item)
     };
     // per-thread byte offsets of its W items inside a chunk slab (loop-invariant).  COT == 4 consumes the slab whole
     // (a linear copy): ONE register, the item stride goes into soffset.
@@ -377,9 +407,43 @@ __global__ __launch_bounds__(512, 2) void conv_tangent_bf16x3_kernel(cmf_conv_ta
 #pragma unroll
     for (int j = 0; j < 8; ++j) r0.f[j] = r1.f[j] = r2.f[j] = 0.f;  // stays 0 when fmode == NONE (never loaded)
 
+    [[maybe_unused]] auto prefetch_mask = [&](Regs& r) {
+      asm volatile("s_nop 4\n\tbuffer_load_ubyte %0, %1, %2, %3 offen" : "=&v"(r.f[0]) : "v"(mo), "s"(frs), "s"(mcur_ch) : "memory");
+      if (++mcur_ch == nchunks) {                                  // the X cursor's rule (below), three chunks earlier
+        mcur_ch = 0;
+        if (mcur_item + 1 < n_items) mset_item(++mcur_item);
+        else mcur_ch = nchunks - 1;
+      }
+    };
     auto prefetch = [&](Regs& r) {
       const int ch = cur_ch;
-      {
+      if constexpr (BITS) {
+        const int s0 = 4 * (ch * 8 + 0) * x_ci, s1 = 4 * (ch * 8 + 1) * x_ci, s2 = 4 * (ch * 8 + 2) * x_ci,
+                  s3 = 4 * (ch * 8 + 3) * x_ci, s4 = 4 * (ch * 8 + 4) * x_ci, s5 = 4 * (ch * 8 + 5) * x_ci,
+                  s6 = 4 * (ch * 8 + 6) * x_ci, s7 = 4 * (ch * 8 + 7) * x_ci;
+        const unsigned mb = __builtin_bit_cast(unsigned, r.f[0]);   // this chunk's byte: loaded three prefetches ago, landed (above)
+        int o[8];
+#pragma unroll
+        for (int j = 0; j < 8; ++j) {
+          const int t = __builtin_amdgcn_sbfe(mb, j, 1);            // 0 / -1
+          o[j] = (xo & t) | (X_DROP & ~t);
+        }
+        asm volatile(
+            "s_nop 4\n\t"
+            "buffer_load_dwordx4 %0, %8, %16, %17 offen\n\t"
+            "buffer_load_dwordx4 %1, %9, %16, %18 offen\n\t"
+            "buffer_load_dwordx4 %2, %10, %16, %19 offen\n\t"
+            "buffer_load_dwordx4 %3, %11, %16, %20 offen\n\t"
+            "buffer_load_dwordx4 %4, %12, %16, %21 offen\n\t"
+            "buffer_load_dwordx4 %5, %13, %16, %22 offen\n\t"
+            "buffer_load_dwordx4 %6, %14, %16, %23 offen\n\t"
+            "buffer_load_dwordx4 %7, %15, %16, %24 offen"
+            : "=&v"(r.x[0]), "=&v"(r.x[1]), "=&v"(r.x[2]), "=&v"(r.x[3]), "=&v"(r.x[4]), "=&v"(r.x[5]), "=&v"(r.x[6]),
+              "=&v"(r.x[7])
+            : "v"(o[0]), "v"(o[1]), "v"(o[2]), "v"(o[3]), "v"(o[4]), "v"(o[5]), "v"(o[6]), "v"(o[7]), "s"(xrs), "s"(s0), "s"(s1),
+              "s"(s2), "s"(s3), "s"(s4), "s"(s5), "s"(s6), "s"(s7)
+            : "memory");
+      } else {
         const int s0 = 4 * (ch * 8 + 0) * x_ci, s1 = 4 * (ch * 8 + 1) * x_ci, s2 = 4 * (ch * 8 + 2) * x_ci,
                   s3 = 4 * (ch * 8 + 3) * x_ci, s4 = 4 * (ch * 8 + 4) * x_ci, s5 = 4 * (ch * 8 + 5) * x_ci,
                   s6 = 4 * (ch * 8 + 6) * x_ci, s7 = 4 * (ch * 8 + 7) * x_ci;
@@ -398,8 +462,8 @@ __global__ __launch_bounds__(512, 2) void conv_tangent_bf16x3_kernel(cmf_conv_ta
             : "v"(xo), "s"(xrs), "s"(s0), "s"(s1), "s"(s2), "s"(s3), "s"(s4), "s"(s5), "s"(s6), "s"(s7)
             : "memory");
       }
-      if constexpr (BITS) {                                        // one byte: the chunk's 8 relu' bits of this pixel
-        asm volatile("s_nop 4\n\tbuffer_load_ubyte %0, %1, %2, %3 offen" : "=&v"(r.f[0]) : "v"(fo), "s"(frs), "s"(ch) : "memory");
+      if constexpr (BITS) {
+        prefetch_mask(r);                                          // one byte: the 8 relu' bits of this pixel, three chunks ahead
       } else if (has_f) {
         const int s0 = 4 * (ch * 8 + 0) * f_ci, s1 = 4 * (ch * 8 + 1) * f_ci, s2 = 4 * (ch * 8 + 2) * f_ci,
                   s3 = 4 * (ch * 8 + 3) * f_ci, s4 = 4 * (ch * 8 + 4) * f_ci, s5 = 4 * (ch * 8 + 5) * f_ci,
@@ -429,6 +493,10 @@ __global__ __launch_bounds__(512, 2) void conv_tangent_bf16x3_kernel(cmf_conv_ta
     // hand-counted waits; the "+v" operands make every consumer of the set depend on the wait statement
     constexpr int NW = C::NWIT;
     auto wait_x = [&](Regs& r) {                                   // X,f of `r` landed; W, X,f, W, X,f may still fly
+      // BITS, wait_x of set s = g % 3 in iteration g - 1.  Issued behind the group [8 X of chunk g, byte of chunk g + 3] (iteration
+      // g - 3): W(g - 1), [X, byte](g + 1), W(g), [X, byte](g + 2) = 2 NW + 2 (8 + 1) loads, the immediate below.  vmcnt retires
+      // in order, so the group's last load -- the byte -- has landed too: r.f[0] is an output of this statement and the next
+      // reader of r.f[0] is iteration g's prefetch(set s), which turns it into the offsets of chunk g + 3's X loads.
       if constexpr (BITS)
         asm volatile("s_waitcnt vmcnt(%9)"
                      : "+v"(r.x[0]), "+v"(r.x[1]), "+v"(r.x[2]), "+v"(r.x[3]), "+v"(r.x[4]), "+v"(r.x[5]), "+v"(r.x[6]),
@@ -495,11 +563,11 @@ __global__ __launch_bounds__(512, 2) void conv_tangent_bf16x3_kernel(cmf_conv_ta
 #pragma unroll
         for (int j = 0; j < 8; ++j) {
           const float f = r.f[j];
-          const float m = NOF ? (F16 ? r.okf * xscale : r.okf) : BITS ? (((__builtin_bit_cast(unsigned, r.f[0]) >> j) & 1u) ? r.okf : 0.f)
+          const float m = NOF ? (F16 ? r.okf * xscale : r.okf) : BITS ? 1.f   // BITS: the registers already hold x or 0 (prefetch)
                                : RELU ? (f > 0.f ? r.okf : 0.f)
                                               : r.okf * (fc0 + fc1 * (f > 0.f ? 1.f : 0.f) + f * (fc2 + fc3 * f));
 #pragma unroll
-          for (int c = 0; c < 4; ++c) v[j][c] = (SELF ? fmaxf(r.x[j][c], 0.f) : r.x[j][c]) * m;
+          for (int c = 0; c < 4; ++c) v[j][c] = BITS ? r.x[j][c] : (SELF ? fmaxf(r.x[j][c], 0.f) : r.x[j][c]) * m;
         }
 #pragma unroll
         for (int c = 0; c < 4; ++c) {                              // column q*4 + c: 8 channels -> 16 B hi + 16 B lo
@@ -545,6 +613,13 @@ __global__ __launch_bounds__(512, 2) void conv_tangent_bf16x3_kernel(cmf_conv_ta
     if (n_items > 0) {
       set_item(0);
       wset_item(0);
+      if constexpr (BITS) {                                        // the bytes of chunks 0, 1, 2 before their X loads
+        mset_item(0);
+        prefetch_mask(r0);
+        prefetch_mask(r1);
+        prefetch_mask(r2);
+        asm volatile("s_waitcnt vmcnt(0)" : "+v"(r0.f[0]), "+v"(r1.f[0]), "+v"(r2.f[0])::"memory");
+      }
       prefetch(r0);                                                // chunks 0, 1, 2 (padded past the end of the stream)
       prefetch(r1);
       prefetch(r2);
@@ -767,9 +842,13 @@ __global__ __launch_bounds__(512, 2) void conv_tangent_bf16x3_kernel(cmf_conv_ta
   // residual as a separate tensor would have to be re-read at the store: the accumulators hold residual + product by then.)
   constexpr bool inplace = INPLACE;                            // launcher: a.r == a.y with y's strides, bit mask given
   // (compile-time: as a run-time flag the 4 x 8-tile PLAIN variant spilled 15 VGPRs; 252 / 244 VGPRs this way)
+  // YMASK (forward RELU / BITS launch with a.ymask): the same machinery as a ROW FILTER.  ymask is the relu' bit mask the output's
+  // only reader applies on load; that reader does not fetch the rows whose bit is clear (loader waves above), so they are not
+  // stored: the lane's store goes past the descriptor's range, still counted by vmcnt.  Values are unchanged.
   auto load_omask = [&](const Item& it) __attribute__((always_inline)) {
-    if constexpr (PLAIN) {
-      const unsigned long long base = reinterpret_cast<unsigned long long>(a.fo) + (unsigned long long)it.np * a.fo_np +
+    if constexpr (PLAIN || YMASK) {
+      const unsigned long long base = (YMASK ? reinterpret_cast<unsigned long long>(a.ymask) + (unsigned long long)it.np * a.ymask_np
+                                             : reinterpret_cast<unsigned long long>(a.fo) + (unsigned long long)it.np * a.fo_np) +
                                       (unsigned)(it.cog * 8 + cohalf * 4);
       const unsigned lo = __builtin_amdgcn_readfirstlane((int)(unsigned)base);
       const unsigned hi = __builtin_amdgcn_readfirstlane((int)(unsigned)(base >> 32));
@@ -780,7 +859,7 @@ __global__ __launch_bounds__(512, 2) void conv_tangent_bf16x3_kernel(cmf_conv_ta
         const int off = __builtin_amdgcn_readfirstlane((it.pix0 + (p / C::TW) * a.W + p % C::TW) * stride);
         unsigned w;
         asm volatile("s_load_dword %0, %1, %2\n\ts_waitcnt lgkmcnt(0)" : "=&s"(w) : "s"(sb), "s"(off) : "memory");
-        omask[p] = use_omask ? w : ~0u;
+        omask[p] = (YMASK || use_omask) ? w : ~0u;
       }
     }
   };
@@ -796,6 +875,7 @@ __global__ __launch_bounds__(512, 2) void conv_tangent_bf16x3_kernel(cmf_conv_ta
         if constexpr (inplace) vo = on ? yvoff : Y_DROP;
         else v = on ? v : f32x4{0.f, 0.f, 0.f, 0.f};
       }
+      if constexpr (YMASK) vo = ((omask[p] >> (c * 16 + cl)) & 1u) ? yvoff : Y_DROP;
       if constexpr (BWD) {                                         // undo the scales, then the per-sample relu' of the forward activation
         v = v * oscale;
         const f32x4 mm = c == 0 ? m0 : m1;
@@ -900,7 +980,7 @@ __global__ __launch_bounds__(512, 2) void conv_tangent_bf16x3_kernel(cmf_conv_ta
     return;
 #endif
     constexpr int KS = QUAD ? 3 : 2, NSTEP = KS * PW;              // step t = KS*p + s (pixel-major)
-    if (LAST) load_omask(cur);                                     // PLAIN only: scalar loads, land during this chunk
+    if (LAST) load_omask(cur);                                     // PLAIN / YMASK only: scalar loads, land during this chunk
     const unsigned char* Xh = smem + stage * C::BUF_BYTES;
     const unsigned char* Xl = Xh + C::XS_BYTES;
     const unsigned char* Wh = Xh + 2 * C::XS_BYTES;
@@ -1227,6 +1307,7 @@ int launch(const cmf_conv_tangent_args& a, hipStream_t s) {
 template <int PXW>
 int launch_cot(const cmf_conv_tangent_args& a, hipStream_t s) {
   // co tiles per workgroup: 64 / 32 channels; factor code specialised for self-relu / relu / anything else
+  if (a.ymask) return a.fmode == CMF_F_RELU ? launch<4, PXW, 6>(a, s) : launch<4, PXW, 7>(a, s);   // (validated by the caller)
   if (a.fmode == CMF_F_SELF_RELU) return (a.cout > 32) ? launch<4, PXW, 2>(a, s) : launch<2, PXW, 2>(a, s);
   if (a.fmode == CMF_F_RELU) return (a.cout > 32) ? launch<4, PXW, 1>(a, s) : launch<2, PXW, 1>(a, s);
   if (a.fmode == CMF_F_RELU_BITS) return (a.cout > 32) ? launch<4, PXW, 3>(a, s) : launch<2, PXW, 3>(a, s);
@@ -1290,6 +1371,12 @@ extern "C" int cmf_conv_tangent_bf16x3(const cmf_conv_tangent_args* ap, void* st
     if (a.fo_np % 4 || (uintptr_t)a.fo % 4 || a.fo_np < (long long)a.H * a.W * (a.cout / 8)) return CMF_EINVAL;
   }
   if (a.fmode == CMF_F_RELU_BITS && a.f_np < (long long)a.H * a.W * (a.cin / 8)) return CMF_EINVAL;
+  if (a.ymask) {
+    // store filter: the forward convs with a relu' factor, whole 64-channel groups, every pixel, nothing else in the epilogue;
+    // the mask words are fetched as aligned dwords
+    if ((a.fmode != CMF_F_RELU && a.fmode != CMF_F_RELU_BITS) || a.cout % 64 || a.live || a.fo || a.r || a.bias) return CMF_EINVAL;
+    if (a.ymask_np % 4 || (uintptr_t)a.ymask % 4 || a.ymask_np < (long long)a.H * a.W * (a.cout / 8)) return CMF_EINVAL;
+  }
   if ((a.x_np | a.x_ci | a.x_px | a.x_sl | a.y_sl | a.r_sl) % 4 || ((uintptr_t)a.x % 16) || ((uintptr_t)a.w % 16)) return CMF_EINVAL;
   if ((a.y_np | a.y_co | a.y_px) % 4 || ((uintptr_t)a.y % 16)) return CMF_EINVAL;            // 16-byte stores
   if (a.r && ((a.r_np | a.r_co | a.r_px) % 4 || ((uintptr_t)a.r % 16))) return CMF_EINVAL;    // 16-byte residual loads
@@ -1332,7 +1419,7 @@ extern "C" int cmf_conv_tangent_f16x3_item(const cmf_conv_tangent_args* ap, int 
   if (!ap || (item_channels != 0 && item_channels != 32 && item_channels != 64)) return CMF_EINVAL;
   const cmf_conv_tangent_args& a = *ap;
   if (!a.x || !a.w || !a.y || a.np <= 0 || a.cin <= 0 || a.cout <= 0 || a.H <= 0 || a.W <= 0) return CMF_EINVAL;
-  if (a.taps != 9 || a.cin % 32 || a.nc <= 0 || a.nc % 16 || a.cout % 64 || a.live) return CMF_EINVAL;
+  if (a.taps != 9 || a.cin % 32 || a.nc <= 0 || a.nc % 16 || a.cout % 64 || a.live || a.ymask) return CMF_EINVAL;
   // forward: the input's own relu, no output factor.  backward (data gradient): plain input, the adjoint pack, y = [fo > 0] . conv
   // + r with fo a float tensor laid out like y (fomode CMF_F_SELF_RELU: cmf_conv_tangent's primal-backward form), no bias, no sign bits
   const bool bwd = a.fmode == CMF_F_NONE && a.fo && a.fomode == CMF_F_SELF_RELU;

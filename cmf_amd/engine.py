@@ -391,12 +391,13 @@ def conv_primal(x_ptr_t, x_off, x_b, x_c, x_px, weight, taps, bias, y, y_b, y_c,
 def conv_tangent(x_t, x_off, x_np, x_ci, x_px, weight, taps, y_t, y_np, y_co, y_px, np_, cin, cout, H, W, nc,
                  fmode=F_NONE, f=None, f_np=0, f_ci=0, f_px=0, res_t=None, transpose=False, bias=None, f_group=1,
                  x_sl=16, y_sl=16, precision=None, y_off=0, res_off=0, fo=None, fo_np=0, fo_co=0, fo_px=0, fomode=F_NONE,
-                 mask_out=None, mask_np=0, amax_in=None, amax_out=None, item_channels=0, live=0, res_np=None):
+                 mask_out=None, mask_np=0, amax_in=None, amax_out=None, item_channels=0, live=0, res_np=None, ymask=None):
     """``fo`` = OUTPUT-side factor (reverse sweep, fp32 kernel only); ``y_off`` / ``res_off`` = element offsets into
     ``y_t`` / ``res_t`` (in-place accumulation into a strided view of a larger tensor).  ``precision`` "f16x3": the fp16 split
     kernel of the primal pass (``amax_in`` / ``amax_out``: one-float device tensors, the input-range chain).  ``live`` 1 / 2:
     checkerboard output (split-precision kernel only): the pixels with (row + col) % 2 == live - 1, stored compactly
-    (``res_np``: sample stride of the residual, a FULL image then; the other residual strides are y's)."""
+    (``res_np``: sample stride of the residual, a FULL image then; the other residual strides are y's).  ``ymask`` (a BitMask over
+    the output channels, split-precision kernel only): store filter -- output rows whose bit is clear are not written."""
     lib = _lib.load()
     a = ConvTangentArgs()
     a.x = C.c_void_p(x_t.data_ptr() + 4 * int(x_off)); a.x_np, a.x_ci, a.x_px = int(x_np), int(x_ci), int(x_px)
@@ -432,6 +433,9 @@ def conv_tangent(x_t, x_off, x_np, x_ci, x_px, weight, taps, y_t, y_np, y_co, y_
     a.amax_in, a.amax_out = (_p(amax_in), _p(amax_out)) if f16 else (None, None)
     a.live = int(live)
     assert not live or split, "checkerboard output is the split-precision kernel's"
+    assert ymask is None or split, "the store filter is the split-precision kernel's"
+    if ymask is not None:
+        a.ymask, a.ymask_np = _p(ymask.data), int(ymask.np_bytes)
     a.np, a.cin, a.cout, a.H, a.W, a.nc, a.taps = int(np_), int(cin), int(cout), int(H), int(W), int(nc), int(taps)
     a.bias = _p(bias); a.f_group = int(f_group)
     a.x_sl, a.y_sl, a.r_sl = int(x_sl), int(y_sl), int(y_sl)
@@ -1374,6 +1378,9 @@ def _view_rows(T, view):
 #: checkerboard couplers: last hidden conv and 1x1 conv at the (1 - mask) pixels only (False: every pixel, rounds 1 - 4)
 CHECKERBOARD_TAIL = True
 
+#: evaluation: a residual block's conv1 does not store the rows of its output that conv2 will not fetch (False: every row)
+SKIP_DEAD_ROWS = True
+
 
 def net_tangent(net, T, view, acts, transpose_packs=False, save=None):
     """Push all Jacobian columns of ``T`` through the coupler network; returns the raw tangent of the
@@ -1383,7 +1390,13 @@ def net_tangent(net, T, view, acts, transpose_packs=False, save=None):
     Checkerboard couplers (``view.live``, evaluation only): a checkerboard layer reads (s, t, s-dot, t-dot) at its (1 - mask)
     pixels alone (acl.py:48-66) and the network's last layer is a pointwise 1x1 conv, so the LAST hidden conv (with its residual
     read) and the 1x1 conv run on those pixels only; the returned stack is then COMPACT -- (B, cout * HW/2, nc), pixel (row, col)
-    at row * W/2 + col // 2 -- and carries ``compact = True`` (``AffineCouplingBijection.decode_`` switches index maps)."""
+    at row * W/2 + col // 2 -- and carries ``compact = True`` (``AffineCouplingBijection.decode_`` switches index maps).
+    Dead rows (``SKIP_DEAD_ROWS``, evaluation only): a split-precision launch that takes relu' from a BitMask does not fetch the
+    (channel, pixel) rows of its input whose bit is clear.  ``u``, the output of a block's conv1, has exactly one reader here -- that
+    block's conv2, through relu'(c1) -- so when that reader is such a launch, conv1 gets c1's mask as its store filter and leaves
+    those rows unwritten (they hold whatever the buffer held).  The invariant: *a tensor with unwritten rows is only ever read by a
+    launch that does not fetch those rows*.  Training (``save``) keeps full stores: ``net_cotangent`` and the weight gradients read
+    the saved ``u``."""
     geo, B, nc, dev = view.geom, T.B, T.nc, T.data.device
     if save is not None:
         save.append(_view_rows(T, view))
@@ -1409,9 +1422,12 @@ def net_tangent(net, T, view, acts, transpose_packs=False, save=None):
         u, h2 = new(hid), new(hid)
         compact = (CHECKERBOARD_TAIL and view.live is not None and save is None and fg == 1 and len(blocks) > 0 and hid % 64 == 0
                    and W % 2 == 0 and _use_bf16x3(9, hid, W, False, H, hid))
+        # conv2 of every block (full or checkerboard form) reads u on the split kernel with c1's bit mask: see the docstring
+        filt = SKIP_DEAD_ROWS and save is None and hid % 64 == 0 and _use_bf16x3(9, hid, W, False, H, hid)
         for k, blk in enumerate(blocks):
             a_in, c1 = acts[2 * k], acts[2 * k + 1]
-            conv_tangent(h.data, 0, *hd, blk.conv1.weight, 9, u.data, *hd, B, hid, hid, H, W, nc, x_sl=hsl, y_sl=hsl, **fk(a_in))
+            conv_tangent(h.data, 0, *hd, blk.conv1.weight, 9, u.data, *hd, B, hid, hid, H, W, nc, x_sl=hsl, y_sl=hsl, **fk(a_in),
+                         ymask=c1 if filt and isinstance(c1, BitMask) else None)
             if compact and k + 1 == len(blocks):
                 # the last hidden conv at the live pixels only, stored compactly; its residual read at those pixels of the full h
                 HWc = HW // 2

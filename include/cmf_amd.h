@@ -41,7 +41,9 @@ extern "C" {
 #define CMF_F_RELU_BITS 5 /* relu' from a BIT MASK (cmf_conv_tangent_bf16x3 only): f points to bytes, one per (sample, pixel,
                              8-channel octet): bit j of f[np*f_np + px*(cin/8) + ci/8] = [activation(ci = 8*(ci/8)+j) > 0];
                              f_np in BYTES.  Written by cmf_conv_tangent's mask_out (below): 1/32 of the bytes of the
-                             activation tensor, one byte load per loader thread and chunk instead of eight dwords */
+                             activation tensor, one byte load per loader thread and chunk instead of eight dwords.
+                             A row (np, ci, px, :) of x whose bit is clear is NOT FETCHED and contributes an exact 0: a
+                             non-finite value there does not propagate (with the float factor CMF_F_RELU it does: NaN * 0) */
 
 /* primal epilogues */
 #define CMF_O_NONE  0
@@ -119,6 +121,12 @@ typedef struct {
                                                    1x1 conv behind it is pointwise -- and y is COMPACT: pixel (row, col) is stored at pixel
                                                    index row*(W/2) + col/2 (y_px = stride between compact pixels).  x, f and the residual r
                                                    keep the full H x W image; r is read at the live pixels.                              */
+  const void* ymask; long long ymask_np;        /* cmf_conv_tangent_bf16x3 only (the other entry points reject it), fmode RELU / RELU_BITS, whole
+                                                   64-channel groups, no live / fo / r / bias: STORE FILTER.  A relu' bit mask over the OUTPUT
+                                                   channels in the CMF_F_RELU_BITS layout (byte np*ymask_np + px*(cout/8) + co/8, ymask_np in
+                                                   bytes, both multiples of 4): rows (np, co, px, :) whose bit is clear are NOT WRITTEN -- y keeps
+                                                   whatever it held there.  For an output whose only reader is a CMF_F_RELU_BITS launch with
+                                                   this very mask, which does not fetch those rows.  NULL = store everything.             */
 } cmf_conv_tangent_args;
 /* (A launch with taps == 9, cin <= 2, cout % 64 == 0, no residual / bias / output factor / mask_out and fmode NONE or RAW -- the
  * first conv of a coupler network, networks.py:40-47 -- is an HBM write stream and runs on a VALU kernel instead of the MFMA one:

@@ -4,6 +4,8 @@ the given substrings, over any number of output directories (one counter group p
 
   python tools/pmc_kernel.py --out profiles/r02_pmc_gram_cholesky.json --kernel gram_chol --note "..." DIR [DIR ...]
 
+With several --kernel substrings every one gets its own entry; --mean adds the launch-weighted mean traffic at top level.
+
 Derived figures written next to the raw averages (when the counters are present):
   traffic_bytes_per_launch   2 x FETCH_SIZE + WRITE_SIZE (KiB counters; FETCH doubled: the guide's gfx950 correction)
   mfma_busy_frac             SQ_VALU_MFMA_BUSY_CYCLES / (SIMDs x GRBM_GUI_ACTIVE / 8): share of the kernel's cycles in which a
@@ -34,6 +36,8 @@ ap.add_argument("--kernel", action="append", required=True)
 ap.add_argument("--out", required=True)
 ap.add_argument("--note", default="")
 ap.add_argument("--batch", type=int, default=512)
+ap.add_argument("--mean", action="store_true", help="several --kernel forms of one kernel: write the launch-weighted mean of their "
+                "traffic_bytes_per_launch at top level (what bench.py cites)")
 ap.add_argument("--source", default=None, help="kernel source file: its SHA-256 (first 16 hex digits) is stamped into the summary")
 a = ap.parse_args()
 acc = defaultdict(lambda: defaultdict(list))
@@ -58,10 +62,15 @@ for sub, cs in acc.items():
         e["kernel_cycles"] = m["GRBM_GUI_ACTIVE"] / 8
         e["mfma_busy_frac"] = m["SQ_VALU_MFMA_BUSY_CYCLES"] / (SIMDS * m["GRBM_GUI_ACTIVE"] / 8)
     out["kernels"][sub] = e
-if len(out["kernels"]) == 1:                       # bench.py reads these two keys at top level
+if len(out["kernels"]) == 1:                       # bench.py reads this key at top level
     only = next(iter(out["kernels"].values()))
     for key in ("traffic_bytes_per_launch",):
         if key in only:
             out[key] = only[key]
+elif a.mean and all("traffic_bytes_per_launch" in e for e in out["kernels"].values()):
+    # several forms of ONE kernel (--mean): the top-level figure is the launch-weighted mean over the forms
+    es = list(out["kernels"].values())
+    out["traffic_bytes_per_launch"] = sum(e["launches"] * e["traffic_bytes_per_launch"] for e in es) / sum(e["launches"] for e in es)
+    out["traffic_mean_over"] = {k: e["launches"] for k, e in out["kernels"].items()}
 json.dump(out, open(a.out, "w"), indent=1)
 print(open(a.out).read())
