@@ -496,6 +496,19 @@ class FlowProgram:
         D = int(np.prod(self.tail.x_shape))
         return 4 * nc * (worst + 4 * D)
 
+    def tangent_chunk(self, B):
+        """Samples per sub-batch of a d-column decode sweep over B samples under ``TANGENT_BUDGET``: equal sub-batches, multiples
+        of 16 where possible -- the primal pass groups 16 samples per column slot, and a ragged last sub-batch would run the
+        per-16 paths underfilled."""
+        per = self.tangent_bytes_per_sample(E.ceil16(self.d))
+        chunk = max(1, min(B, self.TANGENT_BUDGET // max(per, 1)))
+        if chunk < B:
+            n = -(-B // chunk)
+            chunk = -(-B // n)
+            if chunk >= 16:
+                chunk = min(chunk + (-chunk) % 16, B)
+        return chunk
+
     def train_bytes_per_sample(self, nc, recompute=False):
         """Tangent bytes a training step keeps per sample for the backward pass: every layer input of every coupler network
         (ResNet: 2 K + 1 hidden tensors), the modified rows, the raw output tangent, plus the working set of one layer.
@@ -862,15 +875,7 @@ class NonSquareHeadDensity(Density):
         chunk = B
         if want_jac:
             E.check_latent_width(prog.d)                 # before the encode: a head that cannot run launches nothing
-            per = prog.tangent_bytes_per_sample(E.ceil16(prog.d))
-            chunk = max(1, min(B, prog.TANGENT_BUDGET // max(per, 1)))
-            if chunk < B:
-                # equal sub-batches, multiples of 16 where possible: the primal pass groups 16 samples per column slot,
-                # and a ragged last sub-batch would run the per-16 paths underfilled
-                n = -(-B // chunk)
-                chunk = -(-B // n)
-                if chunk >= 16:
-                    chunk = min(chunk + (-chunk) % 16, B)
+            chunk = prog.tangent_chunk(B)
         outs = [self._elbo_chunk(x[i:i + chunk], want_lik, want_jac, add_reconstruction, add_diagonal_metric_reg,
                                  add_offdiagonal_metric_reg, likelihood_wt, metric_wt, ood,
                                  None if _pre_logjac is None else _pre_logjac[i:i + chunk])

@@ -797,6 +797,62 @@ def gram_condition(r, d, threshold):
     return r
 
 
+#: samples one workgroup of ``metric_stats_accumulate`` sums before it writes a float64 partial (the fold adds the partials in chunk
+#: order: with the batch size and d this constant fixes the summation order)
+METRIC_STATS_CHUNK = 16
+
+
+def metric_stats_state_size(d):
+    """Doubles in the flat state of ``metric_stats_accumulate``: [S_G (d*d) | S_cos (d*d) | count | skipped]."""
+    return 2 * int(d) * int(d) + 2
+
+
+def metric_stats_workspace_size(B, d, sample_macs=True):
+    """Doubles of workspace one ``metric_stats_accumulate`` call on (B, d, d) needs."""
+    check_latent_width(d)
+    n = _lib.load().cmf_metric_stats_ws(int(d), int(B), METRIC_STATS_CHUNK, int(bool(sample_macs)))
+    _lib.check(min(n, 0), "cmf_metric_stats_ws")
+    return n
+
+
+def metric_stats_accumulate(jtj, state, workspace=None, sample_macs=None):
+    """ADD the (B, d, d) float32 Gram matrices ``jtj`` to the flat float64 ``state`` (``metric_stats_state_size(d)`` doubles, on the
+    device): running sums of G and of the column cosines G_ij / (n_i n_j), n_k = sqrt(G_kk) + 1e-8, and the numbers of samples
+    counted and skipped (a sample counts iff its diagonal is finite and positive).  ``sample_macs`` (B,) float32, optional: each
+    sample's mean |cos_ij| over i != j (NaN where skipped).  ``workspace``: float64, ``metric_stats_workspace_size`` doubles
+    (allocated here when None).  Deterministic (no atomics); no synchronisation."""
+    require_gpu(jtj, "jtj")
+    if jtj.dim() != 3 or jtj.shape[1] != jtj.shape[2] or not jtj.is_contiguous():
+        raise ValueError(f"jtj must be a contiguous (B, d, d) tensor, got {tuple(jtj.shape)}")
+    B, d = jtj.shape[0], jtj.shape[1]
+    check_latent_width(d)
+    if state.dtype != torch.float64 or state.device != jtj.device or not state.is_contiguous() or \
+            state.numel() != metric_stats_state_size(d):
+        raise ValueError(f"state must be {metric_stats_state_size(d)} contiguous float64 values on {jtj.device}")
+    if sample_macs is not None and (sample_macs.dtype != torch.float32 or sample_macs.device != jtj.device
+                                    or not sample_macs.is_contiguous() or sample_macs.numel() != B):
+        raise ValueError(f"sample_macs must be {B} contiguous float32 values on {jtj.device}")
+    if B == 0:
+        return state
+    need = metric_stats_workspace_size(B, d, sample_macs is not None)
+    if workspace is None:
+        workspace = torch.empty(need, dtype=torch.float64, device=jtj.device)
+    elif workspace.dtype != torch.float64 or workspace.device != jtj.device or not workspace.is_contiguous() or \
+            workspace.numel() < need:
+        raise ValueError(f"workspace must be at least {need} contiguous float64 values on {jtj.device}")
+    launch = lambda: _lib.check(_lib.load().cmf_metric_stats_accumulate(
+        _p(jtj), d, B, METRIC_STATS_CHUNK, _p(state), _p(workspace), workspace.numel(), _p(sample_macs), _stream()),
+        "cmf_metric_stats_accumulate")
+    TIMER = _timer()
+    if TIMER is None:
+        launch()
+    else:
+        # per element one conversion, two multiplies, two adds and an abs in float64; bytes: jtj in, the chunk partials out and in
+        n_chunks = -(-B // METRIC_STATS_CHUNK)
+        TIMER.wrap("metric_stats", 6.0 * B * d * d, 4.0 * B * d * d + 16.0 * (n_chunks + 1) * metric_stats_state_size(d), launch)
+    return state
+
+
 def gram_backward(T, jtj, g_logdet=None, g_l1off=None, g_l1diag=None):
     """Cotangent of the Jacobian stack T for a loss with d/d logdet = g_logdet, d/d l1_off = g_l1off, d/d l1_diag =
     g_l1diag (each (B,) or None): what autograd yields through non_square.py:307-308, :280-294, :87-100."""

@@ -319,6 +319,19 @@ int cmf_cholesky_retry(float* jtj, int d, int B, int attempt, float eps0, float*
  * workspace ws of 2 * B * d * d floats, 8-byte aligned (a float64 d x d matrix per sample).  No allocation, no synchronisation. */
 int cmf_gram_condition(const float* jtj, const int* info, int d, int B, float threshold, float* cond, int* flagged_idx,
                        int* flagged_count, float* ws, void* stream);
+/* Dataset-level statistics of the pull-back metric (the reference's visualizer.py:191-198, :305-317): the launch
+ * ADDS the samples of jtj [B][d][d] to  state = [S_G (d*d) | S_cos (d*d) | count | skipped]  (2 d^2 + 2 doubles, 8-byte aligned):
+ *   n_k = sqrt(G_kk) + 1e-8,  cos_ij = G_ij / (n_i n_j), float64 arithmetic on the float32 input;
+ *   a sample is valid iff every G_kk is finite and > 0: valid samples add G to S_G, cos to S_cos and 1 to count, the others
+ *   add 1 to skipped and nothing else;
+ *   sample_macs [B] float32 (or NULL): mean over i != j of |cos_ij| (0 for d = 1), NaN for a skipped sample.
+ * No floating-point atomics: workgroups sum `chunk` (1 .. 64) consecutive samples into ws, a second launch folds the chunks
+ * onto state in chunk order -- the summation order depends on (B, d, chunk) only and repeated call sequences are bit-identical.
+ * ws: caller-owned, 8-byte aligned, ws_doubles >= cmf_metric_stats_ws(d, B, chunk, sample_macs != NULL) doubles (that function
+ * returns CMF_EINVAL for sizes out of range).  1 <= d <= 512.  jtj is only read.  No allocation, no synchronisation.        */
+long long cmf_metric_stats_ws(int d, int B, int chunk, int with_sample_macs);
+int cmf_metric_stats_accumulate(const float* jtj, int d, int B, int chunk, double* state, double* ws, long long ws_doubles,
+                                float* sample_macs, void* stream);
 /* Reverse of the head above for training (autograd through non_square.py:307-308, :280-294, :87-100):
  *   dt(b, r, :) = 2 * t(b, r, :) * (g_logdet[b] * jtj_b^-1 + g_l1off[b] * sign(jtj_b)[i != j]
  *                                   + g_l1diag[b] * sign(jtj_b)[i == j])
