@@ -87,6 +87,7 @@ SIGNATURES = {
     "cmf_gram_condition": (_i, [_fp, _fp, _i, _i, _f, _fp, _fp, _fp, _fp, _fp]),
     "cmf_metric_stats_ws": (_ll, [_i, _i, _i, _i]),
     "cmf_metric_stats_accumulate": (_i, [_fp, _i, _i, _i, _fp, _fp, _ll, _fp, _fp]),
+    "cmf_gram_spectrum": (_i, [_fp, _i, _i, _fp, _fp, _fp, _fp, _fp]),
     "cmf_stanh_backward": (_i, [_fp, _fp, _fp, _fp, _fp, _fp, _fp, _fp, _fp, _i, _i, _i, _fp]),
     "cmf_tanh_cross_terms": (_i, [_fp, _ll, _ll, _fp, _ll, _ll, _fp, _fp, _i, _i, _i, _fp]),
     "cmf_tanh_backward": (_i, [_fp, _fp, _fp, _ll, _fp, _fp]),

@@ -853,6 +853,51 @@ def metric_stats_accumulate(jtj, state, workspace=None, sample_macs=None):
     return state
 
 
+#: widest Gram matrix ``gram_spectrum`` takes: the float64 matrix of a sample lives in LDS (csrc/gram_spectrum.hip)
+SPECTRUM_MAX_WIDTH = 128
+
+
+class SpectrumResult:
+    """Outputs of ``gram_spectrum`` (all on the device): ``eigenvalues`` (B, d) float64 ascending, ``vectors`` (B, d, d) float64
+    (column k belongs to eigenvalue k) or None, ``sweeps`` (B,) int32, ``info`` (B,) int32 (0 converged, 1 sweep cap reached,
+    2 non-finite input: NaN outputs)."""
+    __slots__ = ("eigenvalues", "vectors", "sweeps", "info")
+
+
+def gram_spectrum(jtj, vectors=False):
+    """Eigenvalues (and, with ``vectors``, eigenvectors) of every (d, d) matrix of ``jtj`` (B, d, d) float32, whose lower
+    triangles are read: float64 cyclic Jacobi, one workgroup per sample.  Deterministic per sample; enqueues one
+    launch, no synchronisation."""
+    if not isinstance(jtj, torch.Tensor) or not jtj.is_cuda:
+        raise ValueError(f"jtj must be on the GPU, got {getattr(jtj, 'device', type(jtj).__name__)} (there is no CPU fallback)")
+    if jtj.dtype != torch.float32:
+        raise ValueError(f"jtj must be float32, got {jtj.dtype}")
+    if jtj.dim() != 3 or jtj.shape[1] != jtj.shape[2] or not jtj.is_contiguous():
+        raise ValueError(f"jtj must be a contiguous (B, d, d) tensor, got {tuple(jtj.shape)}"
+                         f"{'' if jtj.is_contiguous() else ' (not contiguous)'}")
+    B, d = jtj.shape[0], jtj.shape[1]
+    if not 1 <= d <= SPECTRUM_MAX_WIDTH:
+        raise ValueError(f"d = {d}: the spectrum kernel supports 1 <= d <= {SPECTRUM_MAX_WIDTH}")
+    r = SpectrumResult()
+    r.eigenvalues = torch.empty(B, d, dtype=torch.float64, device=jtj.device)
+    r.vectors = torch.empty(B, d, d, dtype=torch.float64, device=jtj.device) if vectors else None
+    r.sweeps = torch.empty(B, dtype=torch.int32, device=jtj.device)
+    r.info = torch.empty(B, dtype=torch.int32, device=jtj.device)
+    if B == 0:
+        return r
+    launch = lambda: _lib.check(_lib.load().cmf_gram_spectrum(_p(jtj), d, B, _p(r.eigenvalues), _p(r.vectors), _p(r.sweeps),
+                                                              _p(r.info), _stream()), "cmf_gram_spectrum")
+    TIMER = _timer()
+    if TIMER is None:
+        launch()
+    else:
+        # a nominal 10 sweeps of d (d - 1) / 2 rotations, each 6 float64 FLOP on 2 d entry pairs of A (+ d of V); bytes: jtj in,
+        # the outputs out (the iteration itself runs in LDS)
+        TIMER.wrap("gram_spectrum", B * 10.0 * (d * (d - 1) / 2) * 6.0 * (3 if vectors else 2) * d,
+                   B * (4.0 * d * d + 8.0 * d + (8.0 * d * d if vectors else 0.0) + 8.0), launch)
+    return r
+
+
 def gram_backward(T, jtj, g_logdet=None, g_l1off=None, g_l1diag=None):
     """Cotangent of the Jacobian stack T for a loss with d/d logdet = g_logdet, d/d l1_off = g_l1off, d/d l1_diag =
     g_l1diag (each (B,) or None): what autograd yields through non_square.py:307-308, :280-294, :87-100."""

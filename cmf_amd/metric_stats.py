@@ -20,6 +20,63 @@ __all__ = ["MetricState", "MetricStatistics"]
 COORDINATES = ("latent", "noise")
 
 
+def metric_head(density, coordinates, what):
+    """The one non-square head of ``density`` whose metric ``what`` ("metric statistics", ...) is about, after the checks every
+    consumer of ``gram_batches`` makes in its constructor."""
+    if coordinates not in COORDINATES:
+        raise ValueError(f"coordinates must be one of {COORDINATES}, got {coordinates!r}")
+    heads = [m for m in density.modules() if isinstance(m, NonSquareHeadDensity)]
+    if len(heads) != 1:
+        raise ValueError(f"{what} need a density with one non-square head, found {len(heads)}")
+    if isinstance(heads[0], ManifoldFlowHeadDensity):
+        raise NotImplementedError(f"{what} of the M-flow baseline head are not built (DESIGN 8)")
+    prog = heads[0].program
+    E.check_latent_width(prog.d)
+    if coordinates == "noise":
+        for m in prog.prior:
+            if not isinstance(m, (AffineCouplingBijection, AffineBijection, _ReshapingBijection)):
+                raise NotImplementedError(f"coordinates='noise': the tangent of the prior layer {type(m).__name__} is not built")
+    return heads[0]
+
+
+def gram_batches(density, head, x, coordinates, ident):
+    """The Gram matrices of the samples of ``x``, sub-batch by sub-batch like the log-density path
+    (``FlowProgram.TANGENT_BUDGET``): yields (i, j, jtj) with jtj (j - i, d, d) float32 the metric of x[i:j] in ``coordinates``,
+    as ONE factorisation attempt leaves it (no jitter ever touches it).  Call under ``torch.no_grad()``; enqueues kernels only and
+    leaves ``head.last_gram`` alone.  ``ident``: a dict the caller keeps between calls (the index vector of ``_prior_jacobian``)."""
+    prog, B = head.program, x.shape[0]
+    chunk = prog.tangent_chunk(B)
+    for i in range(0, B, chunk):
+        z_low = density.extract_latent(x[i:i + chunk], earliest_latent=False)
+        eps = _prior_jacobian(head, z_low, ident) if coordinates == "noise" else None
+        _, T = prog.decode(z_low, tangents=True, eps=eps)
+        yield i, min(i + chunk, B), E.gram_cholesky(T, prog.d, 1).jtj
+
+
+def _prior_jacobian(head, z_low, ident):
+    """P = d z_low / d u (B, d, d) at u = prior(z_low): the prior layers in decode order on u with an identity-seeded tangent
+    stack of d columns, under the head's KernelConfig."""
+    prog, (B, d), dev = head.program, z_low.shape, z_low.device
+    if ident.get("device") != dev:
+        ident["device"], ident["index"] = dev, torch.arange(2 * d, dtype=torch.int32, device=dev)
+    rows, tail = ident["index"][:d], ident["index"][d:]
+    with E.scope(head.kernels):
+        u = z_low.clone()
+        for m in prog.prior:
+            u = m.prior_encode(u)
+        T = E.seed_tangent(B, d, E.ceil16(d), "fmajor", rows, d, dev)
+        for m in reversed(prog.prior):
+            if isinstance(m, AffineCouplingBijection):
+                m.decode_(u, T, ncols=d)
+            elif isinstance(m, AffineBijection):
+                # z = (u - shift) e^{-log_scale}: the coupling update with no network tangent scales row f by e^{-s_f}
+                y = torch.cat((m.shift.detach().reshape(1, d), m.log_scale.detach().reshape(1, d)), dim=1)
+                E.acl_tangent(T, None, u, y, None, {"zi": rows, "ti": rows, "si": tail, "n": d})
+                m.decode_(u)
+            # (a reshaping layer of the flat prior is a view: FlowProgram's prior sweeps pass it by as well)
+    return T.to_dense(d).contiguous()
+
+
 class MetricState:
     """The running sums as ONE flat float64 tensor ``[S_G (d*d) | S_cos (d*d) | count | skipped]`` on any device: what
     ``engine.metric_stats_accumulate`` adds to, and everything that needs no kernel -- merging, the all-reduce, finalisation."""
@@ -79,22 +136,10 @@ class MetricStatistics:
     sample whose metric has a non-positive or non-finite diagonal entry: counted in ``skipped``, added to nothing)."""
 
     def __init__(self, density, coordinates="latent"):
-        if coordinates not in COORDINATES:
-            raise ValueError(f"coordinates must be one of {COORDINATES}, got {coordinates!r}")
-        heads = [m for m in density.modules() if isinstance(m, NonSquareHeadDensity)]
-        if len(heads) != 1:
-            raise ValueError(f"metric statistics need a density with one non-square head, found {len(heads)}")
-        if isinstance(heads[0], ManifoldFlowHeadDensity):
-            raise NotImplementedError("metric statistics of the M-flow baseline head are not built (DESIGN 8)")
-        self.density, self.head, self.coordinates = density, heads[0], coordinates
+        self.density, self.head, self.coordinates = density, metric_head(density, coordinates, "metric statistics"), coordinates
         prog = self.head.program
-        E.check_latent_width(prog.d)
-        if coordinates == "noise":
-            for m in prog.prior:
-                if not isinstance(m, (AffineCouplingBijection, AffineBijection, _ReshapingBijection)):
-                    raise NotImplementedError(f"coordinates='noise': the tangent of the prior layer {type(m).__name__} is not built")
         self.state = MetricState(prog.d, device=prog.tail.permutation.device)
-        self._ident = None
+        self._ident = {}
 
     # the state's own operations, so that a loop needs one object ------------------------------------
     def reset(self):
@@ -118,36 +163,7 @@ class MetricStatistics:
         on the device.  Sub-batches like the log-density path (``FlowProgram.TANGENT_BUDGET``); enqueues kernels only -- no copy
         to the host, no synchronisation -- and leaves ``head.last_gram`` alone."""
         E.require_gpu(x)
-        prog, B = self.head.program, x.shape[0]
-        macs = torch.empty(B, dtype=torch.float32, device=x.device)
-        chunk = prog.tangent_chunk(B)
-        for i in range(0, B, chunk):
-            z_low = self.density.extract_latent(x[i:i + chunk], earliest_latent=False)
-            eps = self._prior_jacobian(z_low) if self.coordinates == "noise" else None
-            _, T = prog.decode(z_low, tangents=True, eps=eps)
-            g = E.gram_cholesky(T, prog.d, 1)            # a single attempt: no jitter ever touches the Gram matrix
-            E.metric_stats_accumulate(g.jtj, self.state.flat, sample_macs=macs[i:i + chunk])
+        macs = torch.empty(x.shape[0], dtype=torch.float32, device=x.device)
+        for i, j, jtj in gram_batches(self.density, self.head, x, self.coordinates, self._ident):
+            E.metric_stats_accumulate(jtj, self.state.flat, sample_macs=macs[i:j])
         return macs
-
-    def _prior_jacobian(self, z_low):
-        """P = d z_low / d u (B, d, d) at u = prior(z_low): the prior layers in decode order on u with an identity-seeded tangent
-        stack of d columns, under the head's KernelConfig."""
-        prog, (B, d), dev = self.head.program, z_low.shape, z_low.device
-        if self._ident is None or self._ident.device != dev:
-            self._ident = torch.arange(2 * d, dtype=torch.int32, device=dev)
-        rows, tail = self._ident[:d], self._ident[d:]
-        with E.scope(self.head.kernels):
-            u = z_low.clone()
-            for m in prog.prior:
-                u = m.prior_encode(u)
-            T = E.seed_tangent(B, d, E.ceil16(d), "fmajor", rows, d, dev)
-            for m in reversed(prog.prior):
-                if isinstance(m, AffineCouplingBijection):
-                    m.decode_(u, T, ncols=d)
-                elif isinstance(m, AffineBijection):
-                    # z = (u - shift) e^{-log_scale}: the coupling update with no network tangent scales row f by e^{-s_f}
-                    y = torch.cat((m.shift.detach().reshape(1, d), m.log_scale.detach().reshape(1, d)), dim=1)
-                    E.acl_tangent(T, None, u, y, None, {"zi": rows, "ti": rows, "si": tail, "n": d})
-                    m.decode_(u)
-                # (a reshaping layer of the flat prior is a view: FlowProgram's prior sweeps pass it by as well)
-        return T.to_dense(d).contiguous()

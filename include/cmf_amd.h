@@ -332,6 +332,24 @@ int cmf_gram_condition(const float* jtj, const int* info, int d, int B, float th
 long long cmf_metric_stats_ws(int d, int B, int chunk, int with_sample_macs);
 int cmf_metric_stats_accumulate(const float* jtj, int d, int B, int chunk, double* state, double* ws, long long ws_doubles,
                                 float* sample_macs, void* stream);
+/* Per-sample spectrum of the Gram matrix: the symmetric eigen-decomposition G_b = V_b diag(lambda_b) V_b^T of
+ * jtj [B][d][d] (float32, as cmf_gram_cholesky leaves it after one attempt; only the lower triangle i >= j is read, jtj is never
+ * written), in float64 by the cyclic two-sided Jacobi method with the round-robin ordering, one workgroup per sample.  A pair
+ * (p, q) is rotated iff |a_pq| > 2^-53 sqrt(|a_pp a_qq|); the sweeps end after the first one without a rotation or after
+ * CMF_SPECTRUM_MAX_SWEEPS.
+ *   eigenvalues [B][d] float64: ascending; equal values keep the order of their position on the converged diagonal.  Zero and
+ *     negative eigenvalues are reported as they are.
+ *   vectors [B][d][d] float64 or NULL: column k belongs to eigenvalue k; its component of largest magnitude is positive (lowest
+ *     row index on ties).  For 64 < d the slice of a sample is also its workgroup's working storage during the launch.
+ *   sweeps [B] int32: sweeps executed, the final rotation-free one included (1 for a diagonal input).
+ *   info [B] int32: 0 converged; 1 sweep cap reached (eigenvalues / vectors hold the current diagonal / V); 2 a non-finite entry
+ *     in the lower triangle (eigenvalues and vectors filled with NaN, sweeps = 0).
+ * A sample's outputs are a function of its d x d input alone (no atomics; independent of B, of its position in the batch and of
+ * the order in which workgroups finish), and the eigenvalues are the same bits with and without vectors.
+ * 1 <= d <= 128 (the float64 matrix lives in LDS), B >= 1, eigenvalues and vectors 8-byte aligned, else CMF_EINVAL.  No
+ * allocation, no synchronisation.                                                                                            */
+#define CMF_SPECTRUM_MAX_SWEEPS 64
+int cmf_gram_spectrum(const float* jtj, int d, int B, double* eigenvalues, double* vectors, int* sweeps, int* info, void* stream);
 /* Reverse of the head above for training (autograd through non_square.py:307-308, :280-294, :87-100):
  *   dt(b, r, :) = 2 * t(b, r, :) * (g_logdet[b] * jtj_b^-1 + g_l1off[b] * sign(jtj_b)[i != j]
  *                                   + g_l1diag[b] * sign(jtj_b)[i == j])
