@@ -29,7 +29,9 @@ class ConvTangentArgs(C.Structure):
                 ("bias", _fp), ("f_group", _i), ("x_sl", _ll), ("y_sl", _ll), ("r_sl", _ll),
                 ("fo", _fp), ("fo_np", _ll), ("fo_co", _ll), ("fo_px", _ll), ("fomode", _i),
                 ("mask_out", _fp), ("mask_np", _ll), ("amax_in", _fp), ("amax_out", _fp), ("live", _i),
-                ("ymask", _fp), ("ymask_np", _ll)]
+                ("ymask", _fp), ("ymask_np", _ll),
+                ("head_w", _fp), ("head_cout", _i), ("head_a", _fp), ("head_a_np", _ll), ("head_a_c", _ll), ("head_a_px", _ll),
+                ("head_y", _fp), ("head_y_np", _ll), ("head_y_co", _ll), ("head_y_px", _ll)]
 
 
 class ConvPrimalArgs(C.Structure):

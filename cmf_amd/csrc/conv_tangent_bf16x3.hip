@@ -1356,6 +1356,7 @@ extern "C" int cmf_pack_weight_f16x3(const float* w, void* out, int cout, int ci
 extern "C" int cmf_conv_tangent_bf16x3(const cmf_conv_tangent_args* ap, void* stream) {
   if (!ap) return CMF_EINVAL;
   const cmf_conv_tangent_args& a = *ap;
+  if (a.head_w) return cmf_conv_head(a, (hipStream_t)stream);   // folded head: the last hidden conv and the 1x1 conv behind it (conv_head.hip)
   if (!a.x || !a.w || !a.y || a.np <= 0 || a.cin <= 0 || a.cout <= 0 || a.H <= 0 || a.W <= 0) return CMF_EINVAL;
   if (a.taps != 9 || a.cin % 32 || a.nc <= 0 || a.nc % 16) return CMF_EINVAL;   // K packing works on groups of 4 octets
   if (a.fmode < CMF_F_NONE || a.fmode > CMF_F_RELU_BITS) return CMF_EINVAL;

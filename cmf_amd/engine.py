@@ -391,15 +391,24 @@ def conv_primal(x_ptr_t, x_off, x_b, x_c, x_px, weight, taps, bias, y, y_b, y_c,
 def conv_tangent(x_t, x_off, x_np, x_ci, x_px, weight, taps, y_t, y_np, y_co, y_px, np_, cin, cout, H, W, nc,
                  fmode=F_NONE, f=None, f_np=0, f_ci=0, f_px=0, res_t=None, transpose=False, bias=None, f_group=1,
                  x_sl=16, y_sl=16, precision=None, y_off=0, res_off=0, fo=None, fo_np=0, fo_co=0, fo_px=0, fomode=F_NONE,
-                 mask_out=None, mask_np=0, amax_in=None, amax_out=None, item_channels=0, live=0, res_np=None, ymask=None):
+                 mask_out=None, mask_np=0, amax_in=None, amax_out=None, item_channels=0, live=0, res_np=None, ymask=None, head=None):
     """``fo`` = OUTPUT-side factor (reverse sweep, fp32 kernel only); ``y_off`` / ``res_off`` = element offsets into
     ``y_t`` / ``res_t`` (in-place accumulation into a strided view of a larger tensor).  ``precision`` "f16x3": the fp16 split
     kernel of the primal pass (``amax_in`` / ``amax_out``: one-float device tensors, the input-range chain).  ``live`` 1 / 2:
     checkerboard output (split-precision kernel only): the pixels with (row + col) % 2 == live - 1, stored compactly
     (``res_np``: sample stride of the residual, a FULL image then; the other residual strides are y's).  ``ymask`` (a BitMask over
-    the output channels, split-precision kernel only): store filter -- output rows whose bit is clear are not written."""
+    the output channels, split-precision kernel only): store filter -- output rows whose bit is clear are not written.
+    ``head`` = dict(weight=<the 1x1 conv's weight (cout', 64, 1, 1)>, act=<float activation (np, 64, H, W) it takes relu' from>):
+    FOLDED HEAD (csrc/conv_head.hip) -- this launch is a coupler network's last hidden conv AND the 1x1 conv behind it; ``y_t`` and
+    its strides then describe the 1x1 conv's output (np, cout', pixels, nc) (compact pixels under ``live``), ``res_t`` the block's
+    input h (slice-major like x, required), ``weight`` goes in raw, and the factor must be a BitMask's."""
     lib = _lib.load()
     a = ConvTangentArgs()
+    if head is not None:
+        assert (precision or cfg().tangent) == "bf16x3" and not transpose and bias is None and fo is None and ymask is None \
+            and mask_out is None, "the folded head replaces the split-precision forward conv + 1x1 conv only"
+        return _conv_tangent_head(lib, a, x_t, x_off, x_np, x_ci, x_px, weight, taps, y_t, y_np, y_co, y_px, np_, cin, cout, H, W, nc,
+                                  fmode, f, f_np, res_t, res_off, res_np, x_sl, y_off, live, head)
     a.x = C.c_void_p(x_t.data_ptr() + 4 * int(x_off)); a.x_np, a.x_ci, a.x_px = int(x_np), int(x_ci), int(x_px)
     a.f = _p(f); a.f_np, a.f_ci, a.f_px = int(f_np), int(f_ci), int(f_px); a.fmode = fmode
     # split-precision kernel: any input factor without output factor, or NO input factor with an optional relu' BIT MASK on the
@@ -460,6 +469,34 @@ def conv_tangent(x_t, x_off, x_np, x_ci, x_px, weight, taps, y_t, y_np, y_co, y_
     TIMER.wrap(f"conv_tangent_t{taps}_ci{cin}_co{cout}" + ("_primal" if fmode == F_SELF_RELU else "_primal_bwd" if pbwd else "_live" if live else ""),
                2.0 * cin * cout * taps * px,
                4.0 * (px_in * cin + px * (cout + (cout if res_t is not None else 0))), launch)
+
+
+def _conv_tangent_head(lib, a, x_t, x_off, x_np, x_ci, x_px, weight, taps, y_t, y_np, y_co, y_px, np_, cin, cout, H, W, nc, fmode, f,
+                       f_np, res_t, res_off, res_np, x_sl, y_off, live, head):
+    """``conv_tangent(..., head=)``: fill the head fields and launch; the C entry validates the shapes (CMF_EINVAL otherwise)."""
+    wf, act = head["weight"], head["act"]
+    hc = int(wf.shape[0])
+    w2, wf = weight.detach(), wf.detach().reshape(hc, -1)
+    assert w2.is_contiguous() and wf.is_contiguous() and act.is_contiguous() and w2.dtype == wf.dtype == act.dtype == torch.float32
+    a.x = C.c_void_p(x_t.data_ptr() + 4 * int(x_off)); a.x_np, a.x_ci, a.x_px, a.x_sl = int(x_np), int(x_ci), int(x_px), int(x_sl)
+    a.f = _p(f); a.f_np = int(f_np); a.fmode = int(fmode)
+    a.w = _p(w2)
+    a.r = None if res_t is None else C.c_void_p(res_t.data_ptr() + 4 * int(res_off))
+    a.r_np, a.r_co, a.r_px, a.r_sl = int(x_np if res_np is None else res_np), int(x_ci), int(x_px), int(x_sl)
+    a.np, a.cin, a.cout, a.H, a.W, a.nc, a.taps, a.live = int(np_), int(cin), int(cout), int(H), int(W), int(nc), int(taps), int(live)
+    a.head_w, a.head_cout = _p(wf), hc
+    a.head_a = _p(act); a.head_a_np, a.head_a_c, a.head_a_px = int(cin) * H * W, H * W, 1
+    a.head_y = C.c_void_p(y_t.data_ptr() + 4 * int(y_off)); a.head_y_np, a.head_y_co, a.head_y_px = int(y_np), int(y_co), int(y_px)
+    launch = lambda: _lib.check(lib.cmf_conv_tangent_bf16x3(C.byref(a), _stream()), "cmf_conv_tangent_bf16x3")
+    TIMER = _timer()
+    if TIMER is None:
+        return launch()
+    # what the launch executes: per output pixel hc * 64 * 576 FMAs for E, then hc * 640 per column; u crosses HBM once (counted
+    # whole: the live fraction is data), h at the output pixels, the activation and yt
+    px_out = float(H) * W * np_ * (0.5 if live else 1.0)
+    TIMER.wrap(f"conv_tangent_t{taps}_ci{cin}_co{cout}" + ("_live" if live else ""),
+               2.0 * hc * px_out * (cin * taps * cout + (cin * taps + cout) * nc),
+               4.0 * (float(H) * W * np_ * nc * cin + px_out * (nc * cout + cout + nc * hc)), launch)
 
 
 _WGRAD_WS = {}
@@ -1482,6 +1519,10 @@ CHECKERBOARD_TAIL = True
 #: evaluation: a residual block's conv1 does not store the rows of its output that conv2 will not fetch (False: every row)
 SKIP_DEAD_ROWS = True
 
+#: evaluation, split-precision tangents on 64-channel couplers: the last hidden conv and the 1x1 output conv run as ONE fp32 launch
+#: that never forms the 64 hidden channels (False: two launches and a gather of the last activation)
+FOLD_HEAD = True
+
 
 def net_tangent(net, T, view, acts, transpose_packs=False, save=None):
     """Push all Jacobian columns of ``T`` through the coupler network; returns the raw tangent of the
@@ -1525,10 +1566,26 @@ def net_tangent(net, T, view, acts, transpose_packs=False, save=None):
                    and W % 2 == 0 and _use_bf16x3(9, hid, W, False, H, hid))
         # conv2 of every block (full or checkerboard form) reads u on the split kernel with c1's bit mask: see the docstring
         filt = SKIP_DEAD_ROWS and save is None and hid % 64 == 0 and _use_bf16x3(9, hid, W, False, H, hid)
+        # folded head: the last block's conv2 and the 1x1 conv as one launch that never forms h_K (csrc/conv_head.hip).  Checkerboard
+        # couplers only: on every pixel of a 14 x 14 image the folded launch did not beat the two launches by more than their own
+        # run-to-run spread (profiles/fold_head.txt), so the split-channel couplers keep them.  (The full-image form these couplers
+        # take under CHECKERBOARD_TAIL = False exists to keep that off-switch bit-neutral: it is not a speed claim.)
+        fold = (FOLD_HEAD and view.live is not None and save is None and fg == 1 and len(blocks) > 0 and hid == 64 and cout <= 8 and nc % 16 == 0
+                and isinstance(acts[2 * len(blocks) - 1], BitMask) and _use_bf16x3(9, hid, W, False, H, hid))
         for k, blk in enumerate(blocks):
             a_in, c1 = acts[2 * k], acts[2 * k + 1]
             conv_tangent(h.data, 0, *hd, blk.conv1.weight, 9, u.data, *hd, B, hid, hid, H, W, nc, x_sl=hsl, y_sl=hsl, **fk(a_in),
                          ymask=c1 if filt and isinstance(c1, BitMask) else None)
+            if fold and k + 1 == len(blocks):
+                # compact (checkerboard) or full output, the same arithmetic per pixel: CHECKERBOARD_TAIL stays bit-neutral
+                HWo = HW // 2 if compact else HW
+                yt = Tangent(B, cout * HWo, nc, "panel", dev)
+                conv_tangent(u.data, 0, *hd, blk.conv2.weight, 9, yt.data, cout * HWo * nc, HWo * nc, nc, B, hid, hid, H, W, nc,
+                             res_t=h.data, res_np=hd[0], x_sl=hsl, live=view.live["parity"] if compact else 0,
+                             head=dict(weight=convf.weight, act=acts[-1]), **fk(c1))
+                if compact:
+                    yt.compact = True
+                return yt
             if compact and k + 1 == len(blocks):
                 # the last hidden conv at the live pixels only, stored compactly; its residual read at those pixels of the full h
                 HWc = HW // 2

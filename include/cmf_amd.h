@@ -127,6 +127,21 @@ typedef struct {
                                                    bytes, both multiples of 4): rows (np, co, px, :) whose bit is clear are NOT WRITTEN -- y keeps
                                                    whatever it held there.  For an output whose only reader is a CMF_F_RELU_BITS launch with
                                                    this very mask, which does not fetch those rows.  NULL = store everything.             */
+  const float* head_w; int head_cout;           /* cmf_conv_tangent_bf16x3 only: FOLDED HEAD (csrc/conv_head.hip).  head_w != NULL turns the launch
+                                                   into a coupler network's last hidden conv AND the 1x1 output conv behind it (networks.py:50-60,
+                                                   jvp_layers.py:38-64), without ever forming the hidden conv's 64 output channels:
+                                                     yt(np, o, p, :) = sum_c G(o,c,p) r(np, c, p, :) + sum_{tap,ci} E(o,p,tap,ci) F(np, ci, p+tap) x(np, ci, p+tap, :)
+                                                     G(o,c,p) = head_w[o][c] [head_a(np, c, p) > 0],   E(o,p,tap,ci) = sum_c G(o,c,p) w[c][ci][tap]
+                                                   in plain fp32 FMAs, per-pixel E built in LDS.  Then: w is the RAW conv weight [64][64][3][3] (not a
+                                                   pack), head_w the raw 1x1 weight [head_cout][64], head_cout <= 8, cin == cout == 64, taps == 9,
+                                                   fmode CMF_F_RELU_BITS (rows of x whose bit is clear are not fetched), x and the residual r both
+                                                   slice-major (x_ci = r_co = 16, x_sl = r_sl = 1024; r = the block's input h, required), live as
+                                                   above, H x W as the split kernel accepts, no bias / fo / ymask / mask_out; y and its strides
+                                                   are ignored.  Anything else: CMF_EINVAL.                                                  */
+  const float* head_a; long long head_a_np, head_a_c, head_a_px;
+                                                /* the float activation the 1x1 conv takes relu' from, (np, 64, H*W), always the FULL image */
+  float* head_y; long long head_y_np, head_y_co, head_y_px;
+                                                /* yt: nc contiguous columns per (np, o, pixel); live != 0: compact pixels, row*(W/2) + col/2 */
 } cmf_conv_tangent_args;
 /* (A launch with taps == 9, cin <= 2, cout % 64 == 0, no residual / bias / output factor / mask_out and fmode NONE or RAW -- the
  * first conv of a coupler network, networks.py:40-47 -- is an HBM write stream and runs on a VALU kernel instead of the MFMA one:
