@@ -45,6 +45,15 @@ class ConvPrimalArgs(C.Structure):
                 ("B", _i), ("cin", _i), ("cout", _i), ("H", _i), ("W", _i), ("taps", _i)]
 
 
+class ProbeApplyArgs(C.Structure):
+    _fields_ = [("r", _fp), ("r_np", _ll), ("r_px", _ll),
+                ("t", _fp), ("t_np", _ll), ("t_c", _ll), ("t_px", _ll),
+                ("cls", _fp),
+                ("y", _fp), ("y_np", _ll), ("y_px", _ll),
+                ("ymask", _fp), ("ymask_np", _ll),
+                ("np", _i), ("cin", _i), ("H", _i), ("W", _i), ("nc", _i), ("ns", _i)]
+
+
 MLP_MAX_LAYERS = 8
 WGRAD_MAX_BATCH = 16
 
@@ -65,6 +74,7 @@ SIGNATURES = {
     "cmf_pack_weight_bf16x3": (_i, [_fp, _fp, _i, _i, C.POINTER(_ll), _fp]),
     "cmf_pack_weight_bf16x3_t": (_i, [_fp, _fp, _i, _i, _i, C.POINTER(_ll), _fp]),
     "cmf_conv_tangent_bf16x3": (_i, [C.POINTER(ConvTangentArgs), _fp]),
+    "cmf_probe_apply": (_i, [C.POINTER(ProbeApplyArgs), _fp]),
     "cmf_pack_weight_f16x3": (_i, [_fp, _fp, _i, _i, _i, C.POINTER(_ll), _fp]),
     "cmf_conv_tangent_f16x3": (_i, [C.POINTER(ConvTangentArgs), _fp]),
     "cmf_conv_tangent_f16x3_item": (_i, [C.POINTER(ConvTangentArgs), _i, _fp]),

@@ -182,8 +182,12 @@ class AffineCouplingBijection(Bijection):
         """Flat element ids of z the coupler network reads (its "pass-through" input)."""
         raise NotImplementedError
 
-    def decode_(self, z, T=None, lj=None, ncols=None, zero_in=False, seed_columns=None):
+    def decode_(self, z, T=None, lj=None, ncols=None, zero_in=False, seed_columns=None, probe=True):
+        """``probe=False``: no probe front (``engine.PROBE_FRONT``) -- the forward pass of a training step, whose backward pass
+        differentiates today's launches."""
         view = self.view(z.device)
+        if not probe:
+            view.probe = None
         if (not zero_in and (T is None or (ncols is not None and ncols <= 15 and lj is None))
                 and E.mlp_coupler_supported(self.net, view, T, 2 * self.cmod)):
             return E.mlp_coupler(self.net, z, T, view, self.maps(z.device), decode=True, lj=lj, ncols=ncols)
@@ -264,7 +268,7 @@ class AffineCouplingBijection(Bijection):
         if not keep and T is not None and not zero_in:
             c = _CouplingCtx(recompute=(z.clone(), E.Tangent(T.B, T.N, T.nc, T.layout, T.data.device,
                                                              data=T.data[: T.B * T.N * T.nc].clone())))
-            self.decode_(z, T)
+            self.decode_(z, T, probe=False)                 # the launches decode_backward rebuilds (save=) and differentiates
             return z, T, c
         view = self.view(z.device)
         acts = E.train_acts_mode(self.net, view, z.shape[0], T, nc=nc_hint) if train else True
@@ -280,7 +284,9 @@ class AffineCouplingBijection(Bijection):
         (T, record of this stack for ``decode_backward`` -- sharing the primal state -- if ``save``, else None).  The low-rank
         Hutchinson backward runs two stacks over one primal decode."""
         c = _CouplingCtx(ctx.x, ctx.y, ctx.g, ctx.acts, ctx.zero_in) if save else ctx
-        self._tangent(T, c, self.view(c.x.device), save=save)
+        view = self.view(c.x.device)
+        view.probe = None                                   # a training step's sweep, saved or not: today's launches
+        self._tangent(T, c, view, save=save)
         return T, (c if save else None)
 
     def decode_vjp(self, Ct, ctx, grads=None, cross=None):
@@ -381,6 +387,7 @@ class Checkerboard2dAffineCouplingBijection(AffineCouplingBijection):
         # compact form of the network's output (engine.net_tangent: last hidden conv and 1x1 conv at the modified pixels only):
         # pixel (row, col) of the (1 - mask) set sits at row * W/2 + col // 2
         self._live = None
+        self._probe_host, self._probe_dev = False, {}                        # False: not built yet
         if W % 2 == 0:
             HW, HWc = H * W, H * W // 2
             livepix = np.flatnonzero(m.reshape(-1) == 0)                      # row-major = compact order (W/2 per row)
@@ -402,7 +409,21 @@ class Checkerboard2dAffineCouplingBijection(AffineCouplingBijection):
             if key not in self._maps._host:
                 self._maps.put(key, (np.arange(hid)[:, None] * self.geom.HW + self._livepix[None, :]).reshape(-1))
             live = {"parity": self._live, "act_idx": self._maps.get(key, device)}
-        return E.NetView(self.geom, cin=self.geom.C, mask=self.mask, live=live)
+        return E.NetView(self.geom, cin=self.geom.C, mask=self.mask, live=live, probe=self._probe(device))
+
+    def _probe(self, device):
+        """The probe front's plan (``engine.probe_plan``) on ``device``, cached beside the index maps; None where there is none."""
+        if self.net.kind != "resnet":
+            return None
+        if self._probe_host is False:
+            self._probe_host = E.probe_plan(self.mask.detach().cpu().numpy())
+        if self._probe_host is None:
+            return None
+        key = str(device)
+        if key not in self._probe_dev:
+            self._probe_dev[key] = {"ns": self._probe_host["ns"], "cls": torch.from_numpy(self._probe_host["cls"]).to(device),
+                                    "probes": torch.from_numpy(self._probe_host["probes"]).reshape(-1).to(device)}
+        return self._probe_dev[key]
 
     def compact_maps(self, device):
         return {"zi": self._maps.get("zi", device), "si": self._maps.get("c_si", device), "ti": self._maps.get("c_ti", device),

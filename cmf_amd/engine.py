@@ -1310,8 +1310,10 @@ def elbo_combine(low, logdet, rec, l1, pre, wl, lam, wm, B, device):
 class NetView:
     """Where a coupler network reads its input inside the current primal / tangent tensors."""
 
-    def __init__(self, geom, cin, chan_off=0, chan_step=1, mask=None, live=None):
+    def __init__(self, geom, cin, chan_off=0, chan_step=1, mask=None, live=None, probe=None):
         self.geom, self.cin, self.chan_off, self.chan_step, self.mask = geom, cin, chan_off, chan_step, mask
+        #: probe front of a masked coupler (``probe_plan`` on the device: {"cls": int8, "ns": int, "probes": float32}) or None
+        self.probe = probe
         #: checkerboard couplers: {"parity": 1 | 2, "act_idx": int32 map (hid * HW/2,) gathering the live pixels of a (hid, H, W)
         #: activation} -- the network's output is read at the pixels with (row + col) % 2 == parity - 1 only (net_tangent)
         self.live = live
@@ -1524,6 +1526,98 @@ SKIP_DEAD_ROWS = True
 FOLD_HEAD = True
 
 
+#: evaluation, split-precision tangents on 64-channel checkerboard couplers: block 0's conv1 runs on one probe column per input
+#: class (13 per input channel) and csrc/probe_front.hip applies the responses to the real columns (False: conv1 on every column)
+PROBE_FRONT = True
+
+#: (H, W, cin) at which the probe front beat today's launch by more than 3 x the run-to-run spread (profiles/probe_front.txt)
+PROBE_FRONT_SHAPES = {(28, 28, 1)}
+
+PROBE_CLASSES = 13
+
+
+def probe_plan(mask):
+    """Host plan of the probe front for a coupler whose network reads ``mask . v``; ``mask`` (cin, H, W) array, != 0 = an input row.
+    Class of input row (c, r, col):  13 c + ((r - 5 col) mod 26 >> 1)  -- on either parity of the checkerboard these are the cosets
+    of the lattice <(5, 1), (-1, 5)>, whose members are at Chebyshev distance >= 5 from each other, so a 5 x 5 window (the support of
+    two stacked 3 x 3 convs) holds every class at most once.  Returns None unless that separation holds for THIS mask (checked by
+    brute force: a mask that is not a checkerboard fails it), else a dict:
+      cls (cin * H * W,) int8: the class, -1 where mask == 0;   ns = ceil(13 cin / 16): 16-column slices of probe columns;
+      probes (cin * H * W, 16 ns) float32: the probe tangent in panel layout, column k = the sum of the unit impulses of class k."""
+    mask = np.asarray(mask)
+    if mask.ndim != 3:
+        return None
+    cin, H, W = mask.shape
+    if not 1 <= cin <= 2:
+        return None
+    r, col = np.meshgrid(np.arange(H), np.arange(W), indexing="ij")
+    cls = (np.mod(r - 5 * col, 2 * PROBE_CLASSES) >> 1)[None] + PROBE_CLASSES * np.arange(cin)[:, None, None]
+    cls = np.where(mask != 0, cls, -1).astype(np.int8)
+    # separation: every 5 x 5 window, clipped at the image border, holds each class at most once
+    for r0 in range(H):
+        for c0 in range(W):
+            win = cls[:, max(r0 - 2, 0):r0 + 3, max(c0 - 2, 0):c0 + 3].reshape(-1)
+            win = win[win >= 0]
+            if len(np.unique(win)) != len(win):
+                return None
+    ns = (PROBE_CLASSES * cin + 15) // 16
+    flat = cls.reshape(-1)
+    probes = np.zeros((cin * H * W, 16 * ns), dtype=np.float32)
+    rows = np.flatnonzero(flat >= 0)
+    probes[rows, flat[rows]] = 1.0
+    return {"cls": flat, "ns": ns, "probes": probes}
+
+
+def probe_apply(R, r_np, r_px, T, t_off, t_np, t_c, t_px, cls, y, y_np, y_px, np_, cin, H, W, nc, ns, ymask=None):
+    """``cmf_probe_apply`` (csrc/probe_front.hip): u0 from the probe responses ``R`` and the input rows of ``T``; ``ymask`` (a BitMask
+    over the 64 output channels): rows whose bit is clear are neither computed nor written."""
+    a = _lib.ProbeApplyArgs()
+    a.r = _p(R); a.r_np, a.r_px = int(r_np), int(r_px)
+    a.t = C.c_void_p(T.data_ptr() + 4 * int(t_off)); a.t_np, a.t_c, a.t_px = int(t_np), int(t_c), int(t_px)
+    a.cls = _p(cls)
+    a.y = _p(y); a.y_np, a.y_px = int(y_np), int(y_px)
+    if ymask is not None:
+        a.ymask, a.ymask_np = _p(ymask.data), int(ymask.np_bytes)
+    a.np, a.cin, a.H, a.W, a.nc, a.ns = int(np_), int(cin), int(H), int(W), int(nc), int(ns)
+    launch = lambda: _lib.check(_lib.load().cmf_probe_apply(C.byref(a), _stream()), "cmf_probe_apply")
+    TIMER = _timer()
+    if TIMER is None:
+        return launch()
+    # <= 13 cin FMAs per output element; u0 is written and R read once (counted whole: the live fraction is data)
+    px = float(H) * W * np_
+    TIMER.wrap(f"probe_apply_ci{cin}", 2.0 * PROBE_CLASSES * cin * 64 * nc * px, 4.0 * px * 64 * (nc + 16 * ns), launch)
+
+
+def _probe_hidden(conv0, view, plan, H, W, hid, dev):
+    """conv0's tangent of the probe columns, (1, HW, ns, hid, 16) slice-major: a function of conv0's weight and the mask alone, so it is
+    computed for ONE sample per parameter version (the thin kernel's arithmetic per element does not depend on the batch) and block
+    0's conv1 reads it with sample stride 0."""
+    HW, ncp = H * W, 16 * plan["ns"]
+
+    def build():
+        out = torch.empty(HW * hid * ncp, dtype=torch.float32, device=dev)
+        conv_tangent(plan["probes"], 0, view.cin * HW * ncp, HW * ncp, ncp, conv0.weight, 9, out, hid * HW * ncp, 16, hid * ncp,
+                     1, view.cin, hid, H, W, ncp, fmode=F_RAW, f=view.mask, f_np=0, f_ci=HW, f_px=1, y_sl=hid * 16)
+        return out
+
+    return DERIVED.get((id(conv0.weight), "probe-front", H, W, view.cin, str(dev)), [conv0.weight], build)
+
+
+def probe_front(conv0, conv1, T, view, plan, factor, ymask, scratch, u, H, W):
+    """u_0 = conv1(relu'(a_0) . conv0(mask . v)) of a 64-channel coupler through the probe columns of ``plan``: conv1 on
+    conv0(probes) -- today's block-0 launch with nc = 16 ns, the same factor (``factor``: conv_tangent's f / fmode keywords) and the
+    same store filter ``ymask`` -- writes the responses R into ``scratch`` (>= B * HW * 64 * 16 ns floats), and the apply kernel
+    turns R and the input rows of ``T`` (panel layout, read through ``view``) into ``u`` (slice-major, rows with a clear bit
+    untouched)."""
+    B, nc, HW, hid, dev = T.B, T.nc, H * W, conv1.out_channels, T.data.device
+    assert hid == 64 and T.layout == "panel"
+    ncp = 16 * plan["ns"]
+    conv_tangent(_probe_hidden(conv0, view, plan, H, W, hid, dev), 0, 0, 16, hid * ncp, conv1.weight, 9, scratch,
+                 hid * HW * ncp, 16, hid * ncp, B, hid, hid, H, W, ncp, x_sl=hid * 16, y_sl=hid * 16, ymask=ymask, **factor)
+    probe_apply(scratch, hid * HW * ncp, hid * ncp, T.data, view.chan_off * HW * nc, T.t_b, view.chan_step * HW * nc, nc,
+                plan["cls"], u, hid * HW * nc, hid * nc, B, view.cin, H, W, nc, plan["ns"], ymask=ymask)
+
+
 def net_tangent(net, T, view, acts, transpose_packs=False, save=None):
     """Push all Jacobian columns of ``T`` through the coupler network; returns the raw tangent of the
     network's pre-activation output (the ScaledTanh derivative ``g`` is applied by acl_tangent).
@@ -1572,10 +1666,21 @@ def net_tangent(net, T, view, acts, transpose_packs=False, save=None):
         # take under CHECKERBOARD_TAIL = False exists to keep that off-switch bit-neutral: it is not a speed claim.)
         fold = (FOLD_HEAD and view.live is not None and save is None and fg == 1 and len(blocks) > 0 and hid == 64 and cout <= 8 and nc % 16 == 0
                 and isinstance(acts[2 * len(blocks) - 1], BitMask) and _use_bf16x3(9, hid, W, False, H, hid))
+        # probe front (csrc/probe_front.hip): block 0's conv1 on the plan's probe columns instead of all nc, then the apply kernel.
+        # Only u_0 changes producer: h_0 on every column is still the thin kernel's (block 0's conv2 reads it as its residual).
+        plan = getattr(view, "probe", None)
+        probe = (PROBE_FRONT and plan is not None and save is None and fg == 1 and len(blocks) > 0 and hid == 64 and view.mask is not None
+                 and T.layout == "panel" and nc % 16 == 0 and nc > 16 * plan["ns"] and (H, W, view.cin) in PROBE_FRONT_SHAPES
+                 and cfg().tangent == "bf16x3" and _use_bf16x3(9, hid, W, False, H, hid))
         for k, blk in enumerate(blocks):
             a_in, c1 = acts[2 * k], acts[2 * k + 1]
-            conv_tangent(h.data, 0, *hd, blk.conv1.weight, 9, u.data, *hd, B, hid, hid, H, W, nc, x_sl=hsl, y_sl=hsl, **fk(a_in),
-                         ymask=c1 if filt and isinstance(c1, BitMask) else None)
+            ym = c1 if filt and isinstance(c1, BitMask) else None
+            if probe and k == 0:
+                # the responses go through h2's buffer: free until conv2 writes it, after the apply kernel has read them
+                probe_front(conv0, blk.conv1, T, view, plan, fk(a_in), ym, h2.data, u.data, H, W)
+            else:
+                conv_tangent(h.data, 0, *hd, blk.conv1.weight, 9, u.data, *hd, B, hid, hid, H, W, nc, x_sl=hsl, y_sl=hsl, **fk(a_in),
+                             ymask=ym)
             if fold and k + 1 == len(blocks):
                 # compact (checkerboard) or full output, the same arithmetic per pixel: CHECKERBOARD_TAIL stays bit-neutral
                 HWo = HW // 2 if compact else HW

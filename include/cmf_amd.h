@@ -163,6 +163,31 @@ int cmf_pack_weight_bf16x3(const float* w, void* out, int cout, int cin, long lo
 int cmf_pack_weight_bf16x3_t(const float* w, void* out, int cout, int cin, int transpose, long long* out_bytes, void* stream);
 int cmf_conv_tangent_bf16x3(const cmf_conv_tangent_args* a, void* stream);
 
+/* Probe front of a checkerboard ResNet coupler's tangent network (evaluation; csrc/probe_front.hip).  The network's first conv
+ * (cin <= 2 -> 64, networks.py:40-47, input mask . v: acl.py:48-52) and block 0's conv1 (64 -> 64, networks.py:62-79) are one linear
+ * map from the input rows v to conv1's output u0 with a 5 x 5 support per output pixel, in which only the pass-through pixels carry
+ * a row.  With the rows coloured so that a 5 x 5 window holds every class at most once, the response R of the two convs to one probe
+ * column per class (the sum of the unit impulses at that class's rows) holds the map's coefficients, and
+ *     y(np, p, sl, co, 0:16) = sum over (dy, dx) in raster order of the window, q = p + (dy, dx) inside the image, c ascending,
+ *                                cls[c*H*W + q] >= 0 of   r(np, p, cls/16, co, cls%16) * t(np, c, q, 16 sl : 16 sl + 16)
+ * in fp32 fmaf, in exactly that order (a column's bits do not depend on its slot, nc or np).
+ *   r   probe responses, [64][16] blocks: element at np*r_np + p*r_px + (cls/16)*1024 + co*16 + cls%16; ns blocks per pixel (1 or 2)
+ *   t   input rows: nc contiguous columns at np*t_np + c*t_c + q*t_px
+ *   cls class table, cin*H*W signed bytes on the device; entries outside [0, 16 ns) mean "no input row here"
+ *   y   slice-major like the hidden tangents: element at np*y_np + p*y_px + (col/16)*1024 + co*16 + col%16
+ *   ymask (or NULL) STORE FILTER as in cmf_conv_tangent_args (byte np*ymask_np + p*8 + co/8, both multiples of 8): a row (np, co, p)
+ *       whose bit is clear is neither computed nor written, and its r row is not fetched (it may hold anything).
+ * cin 1 or 2, 64 output channels, nc % 16 == 0, 16-byte aligned pointers, strides % 4 == 0; else CMF_EINVAL / CMF_ERANGE.           */
+typedef struct {
+  const float* r; long long r_np, r_px;
+  const float* t; long long t_np, t_c, t_px;
+  const signed char* cls;
+  float* y;       long long y_np, y_px;
+  const void* ymask; long long ymask_np;
+  int np, cin, H, W, nc, ns;
+} cmf_probe_apply_args;
+int cmf_probe_apply(const cmf_probe_apply_args* a, void* stream);
+
 /* fp16 split-precision variant for the PRIMAL hidden convs of a ResNet coupler (networks.py:50-60 with 16 samples in the column
  * slots): fmode CMF_F_SELF_RELU, taps == 9, cin % 32 == 0, cout % 64 == 0, tiles as cmf_conv_tangent_bf16x3, no output factor.
  * Operands are split v = hi + lo with hi = fp16(v), lo = fp16(v - hi) (11 + 11 significant bits) and multiplied as
