@@ -1,0 +1,243 @@
+// One damped Gauss-Newton step of the projection onto the manifold, per sample.
+//
+// cmf_gauss_newton_step takes what one decode sweep leaves on the device -- x_hat, the Jacobian stack t (all d columns of J) and
+// the Gram matrix G = J^T J of one cmf_gram_cholesky attempt -- and the head-space input x, and computes in float64
+//   r = x - x_hat,   g = J^T r,   A = G + lambda diag(G)  (Marquardt scaling),   delta = A^-1 g,
+//   stats = { ||r||^2, g^T delta, delta^T G delta, max_k |g_k| }.
+// One 256-thread workgroup per sample; nothing is shared between workgroups, there are no atomics.
+//
+//   1. ||r||^2: thread i sums rows i, i + 256, ... and the 256 partials are folded by a fixed binary tree in LDS.  The
+//      residual-only launch (t == NULL) is this phase alone, so both modes give the same bits.
+//   2. g = J^T r streams J once.  LP = 4, 8, 16 or 32 lanes (the power of two >= min(nc, 128) / 4) run along the column index
+//      with one 16-byte load each, the 256 / LP row groups stride over the rows; every thread keeps four float64 accumulators,
+//      which are folded through LDS in row-group order.  The summation order is a function of (n_rows, nc) alone.  Columns >= d
+//      are padding: lanes that hold none of the first d columns load nothing, and the padding columns a live lane loads are
+//      neither tested for NaN nor folded.
+//   3. The lower triangle of G is loaded into the float64 matrix A in LDS, with g as row d below it, and the diagonal is scaled
+//      by 1 + lambda.  The row stride is d | 1: odd, so that the column reads of the elimination (16 rows of one column per
+//      wave) spread over the banks instead of landing on one.
+//   4. Cholesky without square roots on the lower triangle (the elimination of gram_cond.hip): A_ij -= A_ik A_jk / p_k for
+//      k < j <= i, one barrier per column; the pivots p_k land on the diagonal, column k keeps the unscaled multipliers
+//      L_ik L_kk.  Row d takes part like any other row, which IS the forward substitution: it ends as w_k = y_k L_kk, L y = g.
+//   5. Back substitution on row d, last column first: delta_i = (w_i - sum_{k > i} A_ki delta_k) / p_i, one barrier per column.
+//   6. delta^T G delta from the float32 lower triangle in global memory (A no longer holds G): sum of G_ii delta_i^2 and
+//      2 G_ij delta_i delta_j over i > j, element e of the matrix to thread e mod 256, tree-folded; g^T delta and max |g_k| alike.
+//
+// info: 0 ok; 1 a pivot that is not positive and finite (delta, stats[1], stats[2] = NaN; grad, stats[0], stats[3] valid);
+// 2 a non-finite value in x, x_hat, the first d columns of t or the lower triangle of jtj (every output NaN).
+#include "common.h"
+
+namespace {
+
+constexpr int NT = 256;
+constexpr int MAXD = 128;
+constexpr int PART = 4 * NT;                      // doubles: the J^T r partials [row group][4 LP]; the trees use the first NT
+constexpr int SMALL = PART + MAXD;                // + delta [MAXD]; then A [(d + 1) * row_stride(d)]
+
+inline __host__ __device__ int row_stride(int d) { return d | 1; }
+
+__device__ __forceinline__ bool not_finite(float v) { return !(fabsf(v) <= __FLT_MAX__); }
+
+// Fold one value per thread by a fixed binary tree (sum, or maximum with MAX); the result in every thread.  part: NT doubles
+// that nobody else touches between the two barriers that bracket the call.
+template <bool MAX>
+__device__ __forceinline__ double block_fold(double v, double* part) {
+  const int tid = threadIdx.x;
+  part[tid] = v;
+  __syncthreads();
+  for (int s = NT / 2; s > 0; s >>= 1) {
+    if (tid < s) {
+      const double a = part[tid], c = part[tid + s];
+      part[tid] = MAX ? (c > a ? c : a) : a + c;
+    }
+    __syncthreads();
+  }
+  const double out = part[0];
+  __syncthreads();                                // part may be rewritten by the caller
+  return out;
+}
+
+template <bool FULL>
+__global__ __launch_bounds__(NT) void gn_step_kernel(const float* __restrict__ t, long long t_b, long long t_r, int n_rows, int d,
+                                                      int LP, const float* __restrict__ jtj, const float* __restrict__ x,
+                                                      const float* __restrict__ xhat, const double* __restrict__ damping,
+                                                      double* __restrict__ grad, double* __restrict__ delta,
+                                                      double* __restrict__ stats, int* __restrict__ info) {
+  extern __shared__ __attribute__((aligned(16))) double lds[];
+  const int tid = threadIdx.x, b = blockIdx.x;
+  double* part = lds;
+  const float* __restrict__ xb = x + (long long)b * n_rows;
+  const float* __restrict__ hb = xhat + (long long)b * n_rows;
+  const double nan = __builtin_nan("");
+
+  // 1. ||r||^2
+  int bad = 0;
+  double acc = 0.0;
+  for (int i = tid; i < n_rows; i += NT) {
+    const float a = xb[i], h = hb[i];
+    bad |= not_finite(a) | not_finite(h);
+    const double rr = (double)a - (double)h;
+    acc += rr * rr;
+  }
+  const double r2 = block_fold<false>(acc, part);
+  if (!FULL) {
+    bad = __syncthreads_or(bad);
+    if (tid == 0) {
+      stats[4LL * b] = bad ? nan : r2;
+      info[b] = bad ? 2 : 0;
+    }
+    return;
+  }
+
+  // 2. g = J^T r: the partials of (row group rg, columns c0 .. c0 + 3)
+  double* dl = lds + PART;                        // [MAXD]
+  double* A = lds + SMALL;                        // [(d + 1) * LD]
+  const int LD = row_stride(d);
+  {
+    const int lane = tid & (LP - 1), rg = tid / LP, RG = NT / LP, c0 = 4 * lane;
+    double a0 = 0.0, a1 = 0.0, a2 = 0.0, a3 = 0.0;
+    if (c0 < d) {                                 // c0 + 3 < nc: nc is a multiple of 16 and >= d
+      const bool m1 = c0 + 1 < d, m2 = c0 + 2 < d, m3 = c0 + 3 < d;
+      const float* __restrict__ tp = t + (long long)b * t_b + c0;
+#pragma unroll 4
+      for (int r = rg; r < n_rows; r += RG) {
+        const f32x4 v = *(const f32x4*)(tp + (long long)r * t_r);
+        const double rr = (double)xb[r] - (double)hb[r];
+        bad |= not_finite(v.x) | (m1 & not_finite(v.y)) | (m2 & not_finite(v.z)) | (m3 & not_finite(v.w));
+        a0 += (double)v.x * rr;
+        a1 += (double)v.y * rr;
+        a2 += (double)v.z * rr;
+        a3 += (double)v.w * rr;
+      }
+    }
+    double* p = part + rg * (4 * LP) + c0;        // < PART: rg < RG, c0 + 3 < 4 LP
+    p[0] = a0;
+    p[1] = a1;
+    p[2] = a2;
+    p[3] = a3;
+  }
+
+  // 3. the lower triangle of G
+  const int dd = d * d;
+  const float* __restrict__ G = jtj + (long long)b * dd;
+  for (int e = tid; e < dd; e += NT) {
+    const int i = e / d, j = e - i * d;
+    if (j <= i) {
+      const float v = G[e];
+      bad |= not_finite(v);
+      A[i * LD + j] = (double)v;
+    }
+  }
+  if (__syncthreads_or(bad)) {                    // uniform; the barrier also publishes part and A
+    for (int k = tid; k < d; k += NT) {
+      grad[(long long)b * d + k] = nan;
+      delta[(long long)b * d + k] = nan;
+    }
+    if (tid < 4) stats[4LL * b + tid] = nan;
+    if (tid == 0) info[b] = 2;
+    return;
+  }
+  double gk = 0.0;                                // thread k < d keeps g_k
+  if (tid < d) {
+    const int RG = NT / LP;
+    for (int q = 0; q < RG; ++q) gk += part[q * (4 * LP) + tid];
+    A[d * LD + tid] = gk;
+    grad[(long long)b * d + tid] = gk;
+    const double gkk = A[tid * LD + tid];
+    A[tid * LD + tid] = gkk + damping[b] * gkk;
+  }
+  __syncthreads();
+
+  // 4. pivots and multipliers; row d is g
+  const int ti = tid >> 4, tj = tid & 15;
+  int fail = 0;
+  for (int k = 0; k < d; ++k) {
+    const double piv = A[k * LD + k];             // uniform
+    if (!(piv > 0.0) || !(piv < 1.0e300)) {
+      fail = 1;
+      break;
+    }
+    for (int i = k + 1 + ti; i <= d; i += 16) {
+      const double aik = A[i * LD + k] / piv;      // a division: x / x = 1, a duplicate column cancels its pivot exactly
+      const int jmax = i < d ? i : d - 1;
+      for (int j = k + 1 + tj; j <= jmax; j += 16) A[i * LD + j] -= aik * A[j * LD + k];
+    }
+    __syncthreads();
+  }
+  const double gmax = block_fold<true>(tid < d ? fabs(gk) : 0.0, part);
+  if (fail) {                                     // uniform
+    if (tid < d) delta[(long long)b * d + tid] = nan;
+    if (tid == 0) {
+      stats[4LL * b] = r2;
+      stats[4LL * b + 1] = nan;
+      stats[4LL * b + 2] = nan;
+      stats[4LL * b + 3] = gmax;
+      info[b] = 1;
+    }
+    return;
+  }
+
+  // 5. back substitution on row d
+  double* w = A + d * LD;
+  for (int i = d - 1; i >= 0; --i) {
+    const double di = w[i] / A[i * LD + i];
+    if (tid < i) w[tid] -= A[i * LD + tid] * di;
+    if (tid == i) dl[i] = di;
+    __syncthreads();
+  }
+
+  // 6. the two forms
+  double gd = 0.0, q = 0.0;
+  if (tid < d) {
+    const double dk = dl[tid];
+    delta[(long long)b * d + tid] = dk;
+    gd = gk * dk;
+  }
+  for (int e = tid; e < dd; e += NT) {
+    const int i = e / d, j = e - i * d;
+    if (j <= i) {
+      const double term = (double)G[e] * dl[i] * dl[j];
+      q += j < i ? 2.0 * term : term;
+    }
+  }
+  gd = block_fold<false>(gd, part);
+  q = block_fold<false>(q, part);
+  if (tid == 0) {
+    stats[4LL * b] = r2;
+    stats[4LL * b + 1] = gd;
+    stats[4LL * b + 2] = q;
+    stats[4LL * b + 3] = gmax;
+    info[b] = 0;
+  }
+}
+
+}  // namespace
+
+extern "C" int cmf_gauss_newton_step(const float* t, long long t_b, long long t_r, int n_rows, int nc, int d, int B,
+                                     const float* jtj, const float* x, const float* xhat, const double* damping, double* grad,
+                                     double* delta, double* stats, int* info, void* stream) {
+  if (!x || !xhat || !stats || !info || n_rows <= 0 || B <= 0) return CMF_EINVAL;
+  if ((uintptr_t)x % 4 || (uintptr_t)xhat % 4 || (uintptr_t)stats % 8 || (uintptr_t)info % 4) return CMF_EINVAL;
+  hipStream_t s = (hipStream_t)stream;
+  if (!t) {                                       // residual-only: the Jacobian arguments are not looked at
+    hipLaunchKernelGGL(gn_step_kernel<false>, dim3(B), dim3(NT), NT * sizeof(double), s, nullptr, 0LL, 0LL, n_rows, 0, 0, nullptr,
+                       x, xhat, nullptr, nullptr, nullptr, stats, info);
+    CMF_LAUNCH_CHECK();
+    return 0;
+  }
+  if (!jtj || !damping || !grad || !delta) return CMF_EINVAL;
+  if (d < 1 || d > MAXD || nc % 16 || d > nc) return CMF_EINVAL;
+  if (t_b < nc || t_r < nc || (t_b | t_r) % 4 || (uintptr_t)t % 16) return CMF_EINVAL;
+  if ((uintptr_t)jtj % 4 || (uintptr_t)damping % 8 || (uintptr_t)grad % 8 || (uintptr_t)delta % 8) return CMF_EINVAL;
+  int LP = 4;
+  while (4 * LP < nc && LP < 32) LP <<= 1;
+  const size_t lds = sizeof(double) * ((size_t)SMALL + (size_t)(d + 1) * row_stride(d));
+  if (lds > 48 * 1024) {
+    hipError_t e = cmf_set_dynamic_lds((const void*)gn_step_kernel<true>, (int)lds);
+    if (e != hipSuccess) return (int)e;
+  }
+  hipLaunchKernelGGL(gn_step_kernel<true>, dim3(B), dim3(NT), lds, s, t, t_b, t_r, n_rows, d, LP, jtj, x, xhat, damping, grad, delta,
+                     stats, info);
+  CMF_LAUNCH_CHECK();
+  return 0;
+}

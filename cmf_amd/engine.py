@@ -935,6 +935,102 @@ def gram_spectrum(jtj, vectors=False):
     return r
 
 
+#: widest Jacobian ``gauss_newton_step`` takes: the float64 matrix of a sample lives in LDS (csrc/gn_step.hip)
+PROJECT_MAX_WIDTH = 128
+
+
+class GaussNewtonResult:
+    """Outputs of ``gauss_newton_step`` (all on the device): ``grad`` (B, d) float64 = J^T (x - x_hat), ``delta`` (B, d) float64 =
+    (G + lambda diag G)^-1 grad, ``stats`` (B, 4) float64 = [||x - x_hat||^2, grad^T delta, delta^T G delta, max |grad_k|],
+    ``info`` (B,) int32 (0 ok, 1 non-positive pivot: delta and stats[:, 1:3] NaN, 2 non-finite input: everything NaN)."""
+    __slots__ = ("grad", "delta", "stats", "info")
+
+
+def _residual_pair(x, xhat):
+    """The checks ``gauss_newton_step`` and ``residual_sqnorm`` share; returns (B, elements per sample)."""
+    for name, v in (("x", x), ("xhat", xhat)):
+        if not isinstance(v, torch.Tensor) or not v.is_cuda:
+            raise ValueError(f"{name} must be on the GPU, got {getattr(v, 'device', type(v).__name__)} (there is no CPU fallback)")
+        if v.dtype != torch.float32:
+            raise ValueError(f"{name} must be float32, got {v.dtype}")
+        if v.dim() < 2 or not v.is_contiguous():
+            raise ValueError(f"{name} must be a contiguous (B, ...) tensor, got {tuple(v.shape)}"
+                             f"{'' if v.is_contiguous() else ' (not contiguous)'}")
+    if x.shape != xhat.shape or x.device != xhat.device:
+        raise ValueError(f"x {tuple(x.shape)} on {x.device} and xhat {tuple(xhat.shape)} on {xhat.device} must agree")
+    B = x.shape[0]
+    n = x.numel() // B if B else int(np.prod(x.shape[1:]))
+    if n < 1:
+        raise ValueError(f"x must have at least one element per sample, got {tuple(x.shape)}")
+    return B, n
+
+
+def residual_sqnorm(x, xhat):
+    """||x_b - xhat_b||^2 per sample in float64, by the residual-only mode of the Gauss-Newton step kernel (the same arithmetic,
+    bit for bit, as ``gauss_newton_step(...).stats[:, 0]``): returns ((B,) float64, info (B,) int32 -- 0, or 2 with a NaN norm
+    for a non-finite input).  One launch, no synchronisation."""
+    B, n = _residual_pair(x, xhat)
+    stats = torch.empty(B, 4, dtype=torch.float64, device=x.device)
+    info = torch.empty(B, dtype=torch.int32, device=x.device)
+    if B == 0:
+        return stats[:, 0], info
+    launch = lambda: _lib.check(_lib.load().cmf_gauss_newton_step(None, 0, 0, n, 0, 0, B, None, _p(x), _p(xhat), None, None, None,
+                                                                  _p(stats), _p(info), _stream()), "cmf_gauss_newton_step")
+    TIMER = _timer()
+    if TIMER is None:
+        launch()
+    else:                                          # a subtraction, a multiply and an add per element; x and xhat in
+        TIMER.wrap("residual_sqnorm", 3.0 * B * n, B * (8.0 * n + 12.0), launch)
+    return stats[:, 0], info
+
+
+def gauss_newton_step(T, jtj, x, xhat, damping):
+    """One damped Gauss-Newton step per sample: from the Jacobian stack ``T`` of a decode sweep, its Gram matrix
+    ``jtj`` (B, d, d) float32 (one ``gram_cholesky`` attempt; the lower triangles are read), the head-space input ``x`` and the
+    reconstruction ``xhat`` (B, ...) float32 and ``damping`` (B,) float64 >= 0, in float64: grad = J^T (x - xhat) and delta =
+    (G + damping diag G)^-1 grad.  Returns a ``GaussNewtonResult``.  Deterministic per sample; one launch, no synchronisation."""
+    if not isinstance(T, Tangent):
+        raise ValueError(f"T must be an engine.Tangent, got {type(T).__name__}")
+    B, n = _residual_pair(x, xhat)
+    dev = x.device
+    if not isinstance(jtj, torch.Tensor) or not jtj.is_cuda:
+        raise ValueError(f"jtj must be on the GPU, got {getattr(jtj, 'device', type(jtj).__name__)} (there is no CPU fallback)")
+    if jtj.dtype != torch.float32:
+        raise ValueError(f"jtj must be float32, got {jtj.dtype}")
+    if jtj.dim() != 3 or jtj.shape[1] != jtj.shape[2] or not jtj.is_contiguous():
+        raise ValueError(f"jtj must be a contiguous (B, d, d) tensor, got {tuple(jtj.shape)}"
+                         f"{'' if jtj.is_contiguous() else ' (not contiguous)'}")
+    d = jtj.shape[1]
+    if not 1 <= d <= PROJECT_MAX_WIDTH:
+        raise ValueError(f"d = {d}: the Gauss-Newton step kernel supports 1 <= d <= {PROJECT_MAX_WIDTH}")
+    if T.B != B or T.N != n or T.nc % 16 or T.nc < d or jtj.shape[0] != B or T.data.device != dev or jtj.device != dev:
+        raise ValueError(f"T (B = {T.B}, N = {T.N}, nc = {T.nc}) on {T.data.device} must hold d = {d} <= nc columns, nc % 16 == 0, "
+                         f"for the {B} samples of {n} elements of x on {dev}, like jtj {tuple(jtj.shape)} on {jtj.device}")
+    if not isinstance(damping, torch.Tensor) or damping.dtype != torch.float64 or damping.device != dev or \
+            damping.shape != (B,) or not damping.is_contiguous():
+        raise ValueError(f"damping must be {B} contiguous float64 values on {dev}")
+    r = GaussNewtonResult()
+    r.grad = torch.empty(B, d, dtype=torch.float64, device=dev)
+    r.delta = torch.empty(B, d, dtype=torch.float64, device=dev)
+    r.stats = torch.empty(B, 4, dtype=torch.float64, device=dev)
+    r.info = torch.empty(B, dtype=torch.int32, device=dev)
+    if B == 0:
+        return r
+    launch = lambda: _lib.check(_lib.load().cmf_gauss_newton_step(_p(T.data), T.t_b, T.t_r, n, T.nc, d, B, _p(jtj), _p(x), _p(xhat),
+                                                                  _p(damping), _p(r.grad), _p(r.delta), _p(r.stats), _p(r.info),
+                                                                  _stream()), "cmf_gauss_newton_step")
+    TIMER = _timer()
+    if TIMER is None:
+        launch()
+    else:
+        # float64: J^T r 2 D d, the elimination d^3 / 3 with the two substitutions 2 d^2, the residual 3 D and the two forms
+        # 3 d^2 / 2 + 2 d; bytes: the live quarter-rows of J, x and xhat twice (L2 the second time), the triangle of G twice, the outputs
+        ncl = min(T.nc, -(-d // 4) * 4)
+        TIMER.wrap("gauss_newton_step", B * (2.0 * n * d + d ** 3 / 3.0 + 3.5 * d * d + 3.0 * n + 2.0 * d),
+                   B * (4.0 * n * ncl + 16.0 * n + 4.0 * d * (d + 1) + 16.0 * d + 44.0), launch)
+    return r
+
+
 def gram_backward(T, jtj, g_logdet=None, g_l1off=None, g_l1diag=None):
     """Cotangent of the Jacobian stack T for a loss with d/d logdet = g_logdet, d/d l1_off = g_l1off, d/d l1_diag =
     g_l1diag (each (B,) or None): what autograd yields through non_square.py:307-308, :280-294, :87-100."""

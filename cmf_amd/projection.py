@@ -1,0 +1,128 @@
+"""Projection onto the learned manifold: how far an input is from the image of the decoder g, and the nearest point
+on it.  ``ood()`` answers with the encoder's latent, ||y - g(e(y))||^2 -- an upper bound, because the encoder is a left inverse of
+g, not the orthogonal projection, and the residual it leaves has a component inside the tangent space range(J).
+``ManifoldProjector`` removes that component with a few damped Gauss-Newton (Levenberg-Marquardt) steps on z -> ||y - g(z)||^2,
+started at the encoder's latent.  A step is one decode sweep (x_hat, J), the Gram kernel (J^T J) and one per-sample kernel
+(csrc/gn_step.hip: J^T r and the float64 normal-equation solve); nothing leaves the device.
+
+    proj = cmf_amd.ManifoldProjector(density, steps=10)
+    out = proj.project(x.cuda())
+    out["distance2"], out["initial_distance2"]          # squared distances in the head's input space, after and before
+    out["tangential2"] / out["distance2"]               # share of the remaining residual that is still tangential
+"""
+import torch
+
+from . import engine as E
+from .densities import BijectionDensity, DataParallelDensity, WrapperDensity
+from .metric_stats import metric_head
+
+__all__ = ["ManifoldProjector"]
+
+#: the clamps of the per-sample damping
+DAMPING_MIN, DAMPING_MAX = 1e-12, 1e8
+
+
+def wrapper_bijections(density, head):
+    """The bijections between ``density`` and its ``head``, outermost first: what ``fixed_sample`` inverts on the way out."""
+    chain, node = [], density
+    while node is not head:
+        if isinstance(node, BijectionDensity):
+            chain.append(node.bijection)
+            node = node.prior
+        elif isinstance(node, WrapperDensity):
+            node = node.density
+        elif isinstance(node, DataParallelDensity):
+            node = node.module
+        else:
+            raise NotImplementedError(f"manifold projection through a {type(node).__name__} in front of the head is not built")
+    return chain
+
+
+class ManifoldProjector:
+    """Damped Gauss-Newton projection onto the manifold of a non-square density with latent dimension <= 128.
+
+    ``steps`` iterations per call; every sample carries its own damping lambda, started at ``damping``: a step is accepted iff
+    its solve succeeded and it strictly lowers the distance, then lambda <- max(lambda ``down``, 1e-12); otherwise the sample stays
+    where it is and lambda <- min(lambda ``up``, 1e8).  The distance is therefore monotone non-increasing, and ``steps=0`` gives
+    the diagnostics of the encoder's own latent."""
+
+    def __init__(self, density, steps=10, damping=1e-3, up=10.0, down=0.1):
+        self.density, self.head = density, metric_head(density, "latent", "manifold projection")
+        d = self.head.program.d
+        if d > E.PROJECT_MAX_WIDTH:
+            raise ValueError(f"latent_dimension = {d}: the manifold projection supports 1 <= latent_dimension <= "
+                             f"{E.PROJECT_MAX_WIDTH} (DESIGN 9)")
+        if int(steps) < 0 or not damping >= 0 or not up >= 1 or not 0 < down <= 1:
+            raise ValueError(f"need steps >= 0, damping >= 0, up >= 1 and 0 < down <= 1, got {steps}, {damping}, {up}, {down}")
+        self.steps, self.damping, self.up, self.down = int(steps), float(damping), float(up), float(down)
+        self.chain = wrapper_bijections(density, self.head)
+
+    def head_input_and_latent(self, x):
+        """(y, z): the head's input for ``x`` -- the space in which ``elbo`` / ``ood`` measure the reconstruction term -- and the
+        encoder's latent, from ONE ``extract_latent`` call under a one-shot forward pre-hook on the head."""
+        seen = []
+        handle = self.head.register_forward_pre_hook(lambda module, args: seen.append(args))
+        try:
+            z = self.density.extract_latent(x, earliest_latent=False)
+        finally:
+            handle.remove()
+        mode, y = seen[0][0], seen[0][1]
+        assert len(seen) == 1 and mode == "extract-latent"
+        return y.contiguous(), z.contiguous()
+
+    def evaluate(self, y, z, lam):
+        """Decode with tangents at ``z``, Gram, step kernel: the ``engine.GaussNewtonResult``."""
+        prog = self.head.program
+        x_hat, T = prog.decode(z, tangents=True)
+        jtj = E.gram_cholesky(T, prog.d, 1).jtj
+        return E.gauss_newton_step(T, jtj, y, x_hat.contiguous(), lam)
+
+    @torch.no_grad()
+    def project(self, x, steps=None):
+        """Project every sample of ``x`` (the density's input, as for ``elbo`` / ``ood``; never modified, no dequantisation noise is
+        drawn).  Returns device tensors for the B samples:
+          ``latent`` (B, d) float32; ``reconstruction_head`` (B, *x_shape) = g(latent) in the head's input space and
+          ``reconstruction``, the same mapped back to data space; ``distance2`` and ``initial_distance2`` (B,) float64, the squared
+          distances ||y - g(z)||^2 at the returned and at the encoder's latent; ``tangential2`` (B,) float64 = g^T G^-1 g with
+          g = J^T r at the returned latent, the part of ``distance2`` a better latent could still remove to first order (NaN
+          where the closing ``info`` != 0); ``gradient`` (B, d) float64 = g; ``accepted`` (B,) int32, the steps taken; ``damping``
+          (B,) float64, the final lambda; ``info`` (B,) int32, the code of the closing evaluation (``engine.gauss_newton_step``).
+        Sub-batches like the log-density path; enqueues kernels only -- no copy to the host, no synchronisation -- and leaves
+        ``head.last_gram`` alone."""
+        E.require_gpu(x)
+        steps = self.steps if steps is None else int(steps)
+        prog, B = self.head.program, x.shape[0]
+        if B == 0 or steps < 0:
+            raise ValueError(f"project needs at least one sample and steps >= 0, got {B} samples and steps = {steps}")
+        chunk = prog.tangent_chunk(B)
+        with E.scope(self.head.kernels):
+            parts = [self._project(x[i:i + chunk], steps) for i in range(0, B, chunk)]
+        return parts[0] if len(parts) == 1 else {k: torch.cat([p[k] for p in parts]) for k in parts[0]}
+
+    def _project(self, x, steps):
+        prog, B, dev = self.head.program, x.shape[0], x.device
+        y, z = self.head_input_and_latent(x)
+        x_hat = prog.decode(z, tangents=False)[0].contiguous()
+        d2, _ = E.residual_sqnorm(y, x_hat)
+        d2_0 = d2.clone()
+        lam = torch.full((B,), self.damping, dtype=torch.float64, device=dev)
+        accepted = torch.zeros(B, dtype=torch.int32, device=dev)
+        wide = (B,) + (1,) * (x_hat.dim() - 1)
+        for _ in range(steps):
+            r = self.evaluate(y, z, lam)
+            solved = r.info == 0
+            z_new = z + torch.where(solved[:, None], r.delta, torch.zeros_like(r.delta)).float()
+            x_new = prog.decode(z_new, tangents=False)[0].contiguous()
+            d2_new, _ = E.residual_sqnorm(y, x_new)
+            ok = solved & (d2_new < d2)                               # a NaN distance compares false: rejected
+            z = torch.where(ok[:, None], z_new, z)
+            x_hat = torch.where(ok.view(wide), x_new, x_hat)
+            d2 = torch.where(ok, d2_new, d2)
+            lam = torch.where(ok, (lam * self.down).clamp_min(DAMPING_MIN), (lam * self.up).clamp_max(DAMPING_MAX))
+            accepted += ok
+        r = self.evaluate(y, z, torch.zeros_like(lam))
+        x_data = x_hat
+        for bijection in reversed(self.chain):
+            x_data = bijection.z_to_x(x_data)["x"]
+        return {"latent": z, "reconstruction_head": x_hat, "reconstruction": x_data, "distance2": d2, "initial_distance2": d2_0,
+                "tangential2": r.stats[:, 1].contiguous(), "gradient": r.grad, "accepted": accepted, "damping": lam, "info": r.info}

@@ -390,6 +390,25 @@ int cmf_metric_stats_accumulate(const float* jtj, int d, int B, int chunk, doubl
  * allocation, no synchronisation.                                                                                            */
 #define CMF_SPECTRUM_MAX_SWEEPS 64
 int cmf_gram_spectrum(const float* jtj, int d, int B, double* eigenvalues, double* vectors, int* sweeps, int* info, void* stream);
+/* One damped Gauss-Newton step of the projection onto the manifold, per sample, in float64 on float32 inputs:
+ *   r = x - xhat,  g = J^T r,  A = G + damping[b] diag(G),  delta = A^-1 g  (Cholesky of A in LDS, pivots only).
+ *   t, t_b, t_r, n_rows, nc: the Jacobian stack as cmf_gram_cholesky takes it (both layouts through the two strides); columns
+ *     d .. nc - 1 are padding whose contents influence no output.
+ *   jtj [B][d][d] float32: the Gram matrix as one cmf_gram_cholesky attempt leaves it; only the lower triangle i >= j is read,
+ *     nothing is written.  x, xhat [B][n_rows] float32, contiguous.  damping [B] float64, >= 0.
+ *   grad [B][d], delta [B][d] float64;  stats [B][4] float64 = { ||r||^2, g^T delta, delta^T G delta, max_k |g_k| };
+ *   info [B] int32: 0 ok; 1 a pivot of A was not positive and finite (delta, stats[1], stats[2] are NaN; grad, stats[0], stats[3]
+ *     are valid); 2 a non-finite value in x, xhat, the first d columns of t or the lower triangle of jtj (every output is NaN).
+ * Residual-only mode, t == NULL: only stats[b][0] = ||r||^2 and info[b] (0 or 2) are written -- the same bits as the full mode
+ * gives; t_b, t_r, nc, d are ignored and jtj, damping, grad, delta may be NULL.
+ * A sample's outputs are a function of its own inputs and of (n_rows, nc, d) alone: no atomics, independent of B, of its position
+ * in the batch and of the order in which workgroups finish, and they repeat bit for bit.
+ * With t: 1 <= d <= 128 (the float64 matrix lives in LDS), nc % 16 == 0, d <= nc, t_b and t_r >= nc and % 4 == 0, t 16-byte
+ * aligned; always: n_rows, B >= 1, float64 pointers 8-byte aligned.  Anything else: CMF_EINVAL.  No allocation, no
+ * synchronisation.                                                                                                            */
+int cmf_gauss_newton_step(const float* t, long long t_b, long long t_r, int n_rows, int nc, int d, int B,
+                          const float* jtj, const float* x, const float* xhat, const double* damping,
+                          double* grad, double* delta, double* stats, int* info, void* stream);
 /* Reverse of the head above for training (autograd through non_square.py:307-308, :280-294, :87-100):
  *   dt(b, r, :) = 2 * t(b, r, :) * (g_logdet[b] * jtj_b^-1 + g_l1off[b] * sign(jtj_b)[i != j]
  *                                   + g_l1diag[b] * sign(jtj_b)[i == j])
