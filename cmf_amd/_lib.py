@@ -31,7 +31,8 @@ class ConvTangentArgs(C.Structure):
                 ("mask_out", _fp), ("mask_np", _ll), ("amax_in", _fp), ("amax_out", _fp), ("live", _i),
                 ("ymask", _fp), ("ymask_np", _ll),
                 ("head_w", _fp), ("head_cout", _i), ("head_a", _fp), ("head_a_np", _ll), ("head_a_c", _ll), ("head_a_px", _ll),
-                ("head_y", _fp), ("head_y_np", _ll), ("head_y_co", _ll), ("head_y_px", _ll)]
+                ("head_y", _fp), ("head_y_np", _ll), ("head_y_co", _ll), ("head_y_px", _ll),
+                ("seed", _fp), ("seed_np", _ll), ("seed_col", _ll), ("seed_w", _fp)]
 
 
 class ConvPrimalArgs(C.Structure):
@@ -75,6 +76,8 @@ SIGNATURES = {
     "cmf_pack_weight_bf16x3_t": (_i, [_fp, _fp, _i, _i, _i, C.POINTER(_ll), _fp]),
     "cmf_conv_tangent_bf16x3": (_i, [C.POINTER(ConvTangentArgs), _fp]),
     "cmf_probe_apply": (_i, [C.POINTER(ProbeApplyArgs), _fp]),
+    "cmf_pack_seed_weight": (_i, [_fp, _fp, _fp]),
+    "cmf_seed_panel": (_i, [_fp, _ll, _ll, _fp, _fp, _ll, _ll, _i, _i, _i, _i, _fp]),
     "cmf_pack_weight_f16x3": (_i, [_fp, _fp, _i, _i, _i, C.POINTER(_ll), _fp]),
     "cmf_conv_tangent_f16x3": (_i, [C.POINTER(ConvTangentArgs), _fp]),
     "cmf_conv_tangent_f16x3_item": (_i, [C.POINTER(ConvTangentArgs), _i, _fp]),

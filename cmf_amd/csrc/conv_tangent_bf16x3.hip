@@ -185,7 +185,14 @@ __global__ __launch_bounds__(512, 2) void conv_tangent_bf16x3_kernel(cmf_conv_ta
   // 6 / 7 = RELU / BITS with an OUTPUT row filter (a.ymask: rows the output's only reader will not fetch are not stored; below)
   constexpr bool YMASK = !F16 && (MODE == 6 || MODE == 7);
   static_assert(!YMASK || (COT == 4 && !CKB), "the store filter: whole 64-channel groups, every pixel");
-  constexpr bool SELF = MODE == 2, RELU = MODE == 1 || MODE == 6, BITS = MODE == 3 || MODE == 7;   // 3 = relu' from a bit mask (CMF_F_RELU_BITS)
+  constexpr bool SELF = MODE == 2, RELU = MODE == 1 || MODE == 6, BITS = MODE == 3 || MODE == 7 || MODE == 8;   // 3 = relu' from a bit mask (CMF_F_RELU_BITS)
+  // 8 = BITS with a SEEDED RESIDUAL (a.seed, block 0's conv2 of a checkerboard coupler): the residual h0 = conv0(mask . v) is not read
+  // but formed -- the accumulators of a pixel start at zero and ONE extra K-step in front of the item's first chunk contracts the 9
+  // taps of the one-channel seed panel against conv0's weight (MFMA-wave section below).  That K-step runs on the FP32 MFMA
+  // (v_mfma_f32_16x16x4_f32, three per channel tile): h0 used to come from the thin kernel's fp32 FMAs, and as split bf16 products
+  // its few large terms (one input channel, <= 9 taps) cost 2.7 x the launch's error against float64 (profiles/seed_residual.txt)
+  constexpr bool RSEED = !F16 && MODE == 8;
+  static_assert(!RSEED || (COT == 4 && PXW == 7 && !CKB), "the seeded residual: 64-channel groups on 2 x 14 tiles, every pixel");
   // 4 = PLAIN: no input factor at all (no factor stream, like SELF, and no relu) and an optional OUTPUT-side relu' bit mask
   // applied at the store -- the reverse (cotangent) sweep: the adjoint of "mask, then conv" is "transposed conv, then mask"
   constexpr bool PLAIN = !F16 && (MODE == 4 || MODE == 5);
@@ -729,7 +736,9 @@ __global__ __launch_bounds__(512, 2) void conv_tangent_bf16x3_kernel(cmf_conv_ta
   typedef unsigned bu32x4 __attribute__((vector_size(16)));        // the type the raw buffer builtins use
   constexpr int RS_FLAGS = 0x00020000;
   const int yvoff = 4 * ((cohalf * CW * 16 + cl) * y_co + kq * 4); // lane (kq, cl): columns kq*4..+3 of channel cl (+16c)
-  const int rvoff = 4 * ((cohalf * CW * 16 + cl) * r_co + kq * 4);
+  // RSEED: lane (kq, cl) loads the seed panel's row dy = kq of the pixel's 3 x 3 window for column cl: three consecutive floats
+  // (+ one that is never used) of the column's zero-bordered plane; lane group 3 has no tap: out of the descriptor's range, reads 0
+  const int rvoff = RSEED ? (kq < 3 ? 4 * (cl * (int)a.seed_col + kq * (a.W + 2)) : 0x7ffffff0) : 4 * ((cohalf * CW * 16 + cl) * r_co + kq * 4);
   struct Item {
     int ypix, rpix;                                                // byte offset of pixel p = 0 of this wave's tile row
     int pix0, np, cog;                                             // (PLAIN) pixel index of p = 0, sample, channel group: output mask
@@ -740,7 +749,8 @@ __global__ __launch_bounds__(512, 2) void conv_tangent_bf16x3_kernel(cmf_conv_ta
     const int pix0 = (C::TH * (tile / tiles_x) + wrow) * a.W + C::TW * (tile % tiles_x);
     it.ypix = CKB ? 4 * ((C::TH * (tile / tiles_x) + wrow) * (a.W / 2) + C::TW / 2 * (tile % tiles_x)) * y_px    // compact image
                   : 4 * pix0 * y_px;
-    it.rpix = 4 * pix0 * r_px;
+    it.rpix = RSEED ? 4 * ((C::TH * (tile / tiles_x) + wrow) * (a.W + 2) + C::TW * (tile % tiles_x))   // window corner in the bordered plane
+                    : 4 * pix0 * r_px;
     it.pix0 = pix0, it.np = np, it.cog = cog;
   };
   // descriptors are built from readfirstlane'd words: hipcc otherwise keeps loop-carried descriptors in VGPRs and
@@ -770,12 +780,13 @@ __global__ __launch_bounds__(512, 2) void conv_tangent_bf16x3_kernel(cmf_conv_ta
   const int mvoff = lane < 16 ? lane * (int)a.mask_np : Y_DROP;
   float ymax = 0.f;                                                // F16: running max of the stored values (-> *amax_out)
   auto r_rsrc = [&](int np, int slice, int cog, bool on) {         // words, for the inline-asm loads
-    const float* base = a.r ? a.r + (long long)np * a.r_np + (long long)slice * (a.r_sl ? a.r_sl : 16) + (long long)cog * COG * r_co : a.y;
+    const float* base = RSEED ? a.seed + (long long)np * a.seed_np + (long long)slice * 16 * a.seed_col
+                        : a.r ? a.r + (long long)np * a.r_np + (long long)slice * (a.r_sl ? a.r_sl : 16) + (long long)cog * COG * r_co : a.y;
     const unsigned long long u = reinterpret_cast<unsigned long long>(base);
     i32x4 d;
     d[0] = __builtin_amdgcn_readfirstlane((int)(unsigned)u);
     d[1] = __builtin_amdgcn_readfirstlane((int)((unsigned)(u >> 32) & 0xffffu));
-    d[2] = __builtin_amdgcn_readfirstlane((a.r && on) ? -1 : 0);   // zero records: loads return 0, nothing is fetched
+    d[2] = __builtin_amdgcn_readfirstlane(RSEED ? (on ? 0x7fffff00 : 0) : (a.r && on) ? -1 : 0);   // zero records: loads return 0, nothing is fetched
     d[3] = RS_FLAGS;
     return d;
   };
@@ -809,6 +820,20 @@ __global__ __launch_bounds__(512, 2) void conv_tangent_bf16x3_kernel(cmf_conv_ta
       asm volatile("s_nop 4\n\tbuffer_load_dword %0, %1, %2, %3 offen" : "=v"(bias_h1) : "v"(bvo), "s"(d), "s"(so) : "memory");
     }
   }
+  if constexpr (RSEED) {
+    // conv0's seed pack (4 KiB, cmf_pack_seed_weight) into the LDS behind the centre ring, 16 bytes per MFMA-wave thread; load
+    // and wait are one statement, in front of every hand-counted load of this wave
+    const unsigned long long u = reinterpret_cast<unsigned long long>(a.seed_w);
+    i32x4 d;
+    d[0] = __builtin_amdgcn_readfirstlane((int)(unsigned)u);
+    d[1] = __builtin_amdgcn_readfirstlane((int)((unsigned)(u >> 32) & 0xffffu));
+    d[2] = 4096;
+    d[3] = RS_FLAGS;
+    u32x4 t;
+    const int vo = tid << 4, so = 0;
+    asm volatile("s_nop 4\n\tbuffer_load_dwordx4 %0, %1, %2, %3 offen\n\ts_waitcnt vmcnt(0)" : "=&v"(t) : "v"(vo), "s"(d), "s"(so) : "memory");
+    *reinterpret_cast<u32x4*>(smem + C::LDS_BYTES + (tid << 4)) = t;
+  }
   auto cur_yrs = y_rsrc(np_, slice_, cog_);
   auto cur_mrs = cur_yrs;
   if constexpr (F16) cur_mrs = m_rsrc(np_, slice_, cog_);
@@ -823,6 +848,11 @@ __global__ __launch_bounds__(512, 2) void conv_tangent_bf16x3_kernel(cmf_conv_ta
     i32x4 rrs;
 #pragma unroll
     for (int i = 0; i < 4; ++i) rrs[i] = __builtin_amdgcn_readfirstlane(rrs_in[i]);
+    if constexpr (RSEED) {                                         // ONE load per pixel: the lane's window row, as raw floats
+      const int so = __builtin_amdgcn_readfirstlane(it.rpix + 4 * (trow(p) * (a.W + 2) + tp(p) % C::TW));
+      asm volatile("s_nop 4\n\tbuffer_load_dwordx4 %0, %1, %2, %3 offen" : "=v"(acc[p][0]) : "v"(rvoff), "s"(rrs), "s"(so) : "memory");
+      return;
+    }
 #pragma unroll
     for (int c = 0; c < CW; ++c) {
       const int so = it.rpix + 4 * ((trow(p) * a.W + tp(p) % C::TW + (CKB ? ck_o[trow(p) & 1] : 0)) * r_px + c * 16 * r_co);
@@ -952,10 +982,11 @@ __global__ __launch_bounds__(512, 2) void conv_tangent_bf16x3_kernel(cmf_conv_ta
   // (+ 2*CW*p of THIS chunk's tail when the item has a single chunk).
   auto wait_res = [&](int p, bool also_last) __attribute__((always_inline)) {
     static_assert(CW == 2 || CW == 1, "operand list below");
-    constexpr int NT = 2 * CW + (F16 ? 1 : 0);                     // VMEM operations of one pixel's tail (F16: + the mask store)
+    constexpr int NT = RSEED ? CW + 1 : 2 * CW + (F16 ? 1 : 0);    // VMEM operations of one pixel's tail (F16: + the mask store; RSEED: CW stores, one seed load)
     const int n0 = NT * (PW - 1 - p) + (also_last ? NT * p : 0);
     const int n = n0 > 63 ? 63 : n0;                               // vmcnt is a 6-bit field: waiting for more is always safe
-    if constexpr (CW == 2) asm volatile("s_waitcnt vmcnt(%2)" : "+v"(acc[p][0]), "+v"(acc[p][1]) : "n"(n));
+    if constexpr (RSEED) asm volatile("s_waitcnt vmcnt(%1)" : "+v"(acc[p][0]) : "n"(n));
+    else if constexpr (CW == 2) asm volatile("s_waitcnt vmcnt(%2)" : "+v"(acc[p][0]), "+v"(acc[p][1]) : "n"(n));
     else asm volatile("s_waitcnt vmcnt(%1)" : "+v"(acc[p][0]) : "n"(n));
   };
 
@@ -986,6 +1017,15 @@ __global__ __launch_bounds__(512, 2) void conv_tangent_bf16x3_kernel(cmf_conv_ta
     const unsigned char* Wh = Xh + 2 * C::XS_BYTES;
     const unsigned char* Wl = Wh + C::WS_BYTES;
     bf16x8 ah[KS][CW], al[KS][CW], bh[BD], bl[BD];
+    // RSEED: conv0's weight as B operands of the seed K-step, from the image behind the ring (16 bytes per lane and channel tile:
+    // the lane's three taps).  The FIRST chunk is never a QUAD chunk: these registers are some of those its third K-step would hold.
+    [[maybe_unused]] f32x4 sw[CW];
+    if constexpr (RSEED) {
+      if (FIRST) {
+#pragma unroll
+        for (int c = 0; c < CW; ++c) sw[c] = *reinterpret_cast<const f32x4*>(smem + C::LDS_BYTES + (((cohalf * CW + c) * 64 + lane) << 4));
+      }
+    }
     // centre K-step operands: lane groups 0..2 read the ring (hi at +0, lo at +RING_HALF), group 3 the live stage
     const unsigned char* ch_[2];
     const unsigned char* cl_[2];
@@ -1056,7 +1096,22 @@ __global__ __launch_bounds__(512, 2) void conv_tangent_bf16x3_kernel(cmf_conv_ta
 #pragma unroll
         for (int c = 0; c < CW; ++c) acc[p][c] = f32x4{0.f, 0.f, 0.f, 0.f};
       }
-      if (FIRST && s == 0 && !FRES) {
+      if constexpr (RSEED) {
+        if (FIRST && s == 0) {
+          // the seed K-step: the lane's three taps have landed in acc[p][0] as raw floats and go into the fp32 MFMA as they are --
+          // v_mfma_f32_16x16x4_f32 contracts K = 4 lane groups, MFMA j carries tap 3 kq + j of lane group kq (group 3: zeros) --
+          // starting from zero accumulators; then the item's first chunk as usual
+          wait_res(p, false);
+          const float s0 = acc[p][0][0], s1 = acc[p][0][1], s2 = acc[p][0][2];
+#pragma unroll
+          for (int c = 0; c < CW; ++c) {
+            acc[p][c] = __builtin_amdgcn_mfma_f32_16x16x4f32(s0, sw[c][0], f32x4{0.f, 0.f, 0.f, 0.f}, 0, 0, 0);
+            acc[p][c] = __builtin_amdgcn_mfma_f32_16x16x4f32(s1, sw[c][1], acc[p][c], 0, 0, 0);
+            acc[p][c] = __builtin_amdgcn_mfma_f32_16x16x4f32(s2, sw[c][2], acc[p][c], 0, 0, 0);
+          }
+        }
+      }
+      if (FIRST && s == 0 && !FRES && !RSEED) {
 #ifndef CMF_DBG_SPREAD
         wait_res(p, false);
 #endif
@@ -1284,6 +1339,49 @@ __global__ __launch_bounds__(1024) void pack_f16_scale_kernel(const float* __res
   }
 }
 
+// conv0's weight [64][1][3][3] as the B operands of the seed K-step (MODE 8): out[co tile 4][lane 64][4] fp32, lane = 16 kq + co % 16;
+// element j of lane group kq is tap 3 kq + j (window row kq, column j) for kq, j < 3 and zero otherwise
+__global__ void pack_seed_weight_kernel(const float* __restrict__ w, float* __restrict__ out) {
+  const int i = blockIdx.x * 256 + threadIdx.x;                    // 1024 elements
+  const int j = i & 3, lane = (i >> 2) & 63, cot = i >> 8;
+  const int kq = lane >> 4, co = cot * 16 + (lane & 15);
+  out[i] = (kq < 3 && j < 3) ? w[co * 9 + 3 * kq + j] : 0.f;
+}
+
+// seed panel (MODE 8): out(b, col, r, c) over the zero-bordered (H + 2) x (W + 2) image = mask(r - 1, c - 1) . v(b, r - 1, c - 1, col),
+// an exact 0 on the border, at masked pixels and in the plane's padding.  v has nc contiguous columns per pixel, the panel has the
+// pixels of ONE column contiguous (plane stride seed_col): a 64-pixel x 16-column transpose through LDS per workgroup.
+__global__ __launch_bounds__(256) void seed_panel_kernel(const float* __restrict__ v, long long v_np, long long v_px,
+                                                         const float* __restrict__ mask, float* __restrict__ out, long long o_np,
+                                                         int o_col, int H, int W, int nc) {
+  __shared__ float tile[64][17];
+  const int t = threadIdx.x, p0 = blockIdx.x * 64, c0 = blockIdx.y * 16;
+  const long long b = blockIdx.z;
+  {
+    const int col = t & 15;
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+      const int pl = (t >> 4) + 16 * i, pp = p0 + pl;
+      const int r = pp / (W + 2) - 1, c = pp % (W + 2) - 1;
+      float x = 0.f;
+      if (r >= 0 && r < H && c >= 0 && c < W) {
+        const float m = mask ? mask[r * W + c] : 1.f;
+        if (m != 0.f) x = m * v[b * v_np + (long long)(r * W + c) * v_px + c0 + col];
+      }
+      tile[pl][col] = x;
+    }
+  }
+  __syncthreads();
+  const int pl = t & 63, pp = p0 + pl;
+  if (pp < o_col) {
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+      const int col = (t >> 6) + 4 * j;
+      out[b * o_np + (long long)(c0 + col) * o_col + pp] = tile[pl][col];
+    }
+  }
+}
+
 template <int COT, int PXW, int MODE, bool F16 = false, bool FRES = false, bool CKB = false>
 int launch(const cmf_conv_tangent_args& a, hipStream_t s) {
   using C = BCfg<COT, PXW>;
@@ -1292,7 +1390,7 @@ int launch(const cmf_conv_tangent_args& a, hipStream_t s) {
   const long long total = (long long)tiles * nslices * ncog * a.np;
   if (total > 0x7fffffffLL) return CMF_ERANGE;
   auto k = conv_tangent_bf16x3_kernel<COT, PXW, MODE, F16, FRES, CKB>;
-  constexpr int lds = C::LDS_BYTES;
+  constexpr int lds = C::LDS_BYTES + (MODE == 8 ? 4096 : 0);   // seeded residual: conv0's seed pack behind the centre ring
   if (hipError_t e = cmf_set_dynamic_lds((const void*)k, lds); e != hipSuccess) return (int)e;   // per device (runtime.hip)
   const int n_cu = cmf_device_cus();
   int grid = (int)(total < n_cu ? total : n_cu);                // persistent: one 112 KiB workgroup per CU
@@ -1334,6 +1432,23 @@ extern "C" int cmf_pack_weight_bf16x3_t(const float* w, void* out, int cout, int
   if (!w) return CMF_EINVAL;
   hipLaunchKernelGGL(pack_weight_bf16x3_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, (hipStream_t)stream,
                      w, (unsigned short*)out, cout, cin, total, transpose ? 1 : 0, 0);
+  CMF_LAUNCH_CHECK();
+  return 0;
+}
+
+extern "C" int cmf_pack_seed_weight(const float* w, void* out, void* stream) {
+  if (!w || !out || (uintptr_t)out % 16) return CMF_EINVAL;
+  hipLaunchKernelGGL(pack_seed_weight_kernel, dim3(4), dim3(256), 0, (hipStream_t)stream, w, (float*)out);
+  CMF_LAUNCH_CHECK();
+  return 0;
+}
+
+extern "C" int cmf_seed_panel(const float* v, long long v_np, long long v_px, const float* mask, float* out, long long out_np,
+                              long long out_col, int np, int H, int W, int nc, void* stream) {
+  if (!v || !out || np <= 0 || H <= 0 || W <= 0 || nc <= 0 || nc % 16 || v_px < nc) return CMF_EINVAL;
+  if (out_col < (long long)(H + 2) * (W + 2) + 1 || out_np < out_col * nc || out_col > (1 << 24) || np > 65535) return CMF_EINVAL;
+  hipLaunchKernelGGL(seed_panel_kernel, dim3((unsigned)((out_col + 63) / 64), nc / 16, np), dim3(256), 0, (hipStream_t)stream, v, v_np,
+                     v_px, mask, out, out_np, (int)out_col, H, W, nc);
   CMF_LAUNCH_CHECK();
   return 0;
 }
@@ -1393,6 +1508,16 @@ extern "C" int cmf_conv_tangent_bf16x3(const cmf_conv_tangent_args* ap, void* st
   const bool t14 = a.W % 14 == 0 && a.H % 2 == 0, t8 = a.W % 8 == 0 && a.H % 4 == 0;
   if (!(t14 || t8) || !(a.cout % 64 == 0 || a.cout == 32)) return CMF_EINVAL;
   if (a.bias && a.cout > 64) return CMF_EINVAL;                 // the per-channel constants are fetched once per launch
+  if (a.seed) {
+    // seeded residual (MODE 8): block 0's conv2 of a coupler whose first conv has ONE input channel -- relu' from a bit mask, one
+    // 64-channel group, 2 x 14 tiles, every pixel, nothing in the epilogue; the residual is formed from the seed panel, r is not read
+    if (!a.seed_w || a.r || a.fmode != CMF_F_RELU_BITS || a.cout != 64 || !t14 || a.live || a.ymask || a.fo || a.bias) return CMF_EINVAL;
+    if ((uintptr_t)a.seed % 4 || (uintptr_t)a.seed_w % 16) return CMF_EINVAL;
+    // a lane reads four floats from its window row: one past the last row's end at the image's right border
+    if (a.seed_col < (long long)(a.H + 2) * (a.W + 2) + 1 || a.seed_np < a.seed_col * a.nc) return CMF_EINVAL;
+    if (!fits_int(16 * a.seed_col)) return CMF_ERANGE;
+    return launch<4, 7, 8>(a, s);
+  }
   if (a.live) {
     // checkerboard output: the forward tangent conv with a relu' factor, whole 64-channel groups, nothing in the epilogue but the residual
     if (a.live < 0 || a.live > 2 || (a.fmode != CMF_F_RELU && a.fmode != CMF_F_RELU_BITS) || a.fo || a.bias || a.cout % 64 || a.W % 2)

@@ -391,7 +391,8 @@ def conv_primal(x_ptr_t, x_off, x_b, x_c, x_px, weight, taps, bias, y, y_b, y_c,
 def conv_tangent(x_t, x_off, x_np, x_ci, x_px, weight, taps, y_t, y_np, y_co, y_px, np_, cin, cout, H, W, nc,
                  fmode=F_NONE, f=None, f_np=0, f_ci=0, f_px=0, res_t=None, transpose=False, bias=None, f_group=1,
                  x_sl=16, y_sl=16, precision=None, y_off=0, res_off=0, fo=None, fo_np=0, fo_co=0, fo_px=0, fomode=F_NONE,
-                 mask_out=None, mask_np=0, amax_in=None, amax_out=None, item_channels=0, live=0, res_np=None, ymask=None, head=None):
+                 mask_out=None, mask_np=0, amax_in=None, amax_out=None, item_channels=0, live=0, res_np=None, ymask=None, head=None,
+                 seed=None):
     """``fo`` = OUTPUT-side factor (reverse sweep, fp32 kernel only); ``y_off`` / ``res_off`` = element offsets into
     ``y_t`` / ``res_t`` (in-place accumulation into a strided view of a larger tensor).  ``precision`` "f16x3": the fp16 split
     kernel of the primal pass (``amax_in`` / ``amax_out``: one-float device tensors, the input-range chain).  ``live`` 1 / 2:
@@ -401,7 +402,9 @@ def conv_tangent(x_t, x_off, x_np, x_ci, x_px, weight, taps, y_t, y_np, y_co, y_
     ``head`` = dict(weight=<the 1x1 conv's weight (cout', 64, 1, 1)>, act=<float activation (np, 64, H, W) it takes relu' from>):
     FOLDED HEAD (csrc/conv_head.hip) -- this launch is a coupler network's last hidden conv AND the 1x1 conv behind it; ``y_t`` and
     its strides then describe the 1x1 conv's output (np, cout', pixels, nc) (compact pixels under ``live``), ``res_t`` the block's
-    input h (slice-major like x, required), ``weight`` goes in raw, and the factor must be a BitMask's."""
+    input h (slice-major like x, required), ``weight`` goes in raw, and the factor must be a BitMask's.
+    ``seed`` = dict(panel=, np=, col=, pack=) (``seed_panel`` / ``_seed_pack``): SEEDED RESIDUAL -- the launch is block 0's conv2 and
+    forms its residual conv0(mask . v) itself from the one-channel seed panel; no ``res_t``, the factor must be a BitMask's."""
     lib = _lib.load()
     a = ConvTangentArgs()
     if head is not None:
@@ -445,6 +448,9 @@ def conv_tangent(x_t, x_off, x_np, x_ci, x_px, weight, taps, y_t, y_np, y_co, y_
     assert ymask is None or split, "the store filter is the split-precision kernel's"
     if ymask is not None:
         a.ymask, a.ymask_np = _p(ymask.data), int(ymask.np_bytes)
+    if seed is not None:
+        assert split and res_t is None and fmode == F_RELU_BITS, "the seeded residual is the split-precision kernel's, bit-mask factor"
+        a.seed, a.seed_np, a.seed_col, a.seed_w = _p(seed["panel"]), int(seed["np"]), int(seed["col"]), _p(seed["pack"])
     a.np, a.cin, a.cout, a.H, a.W, a.nc, a.taps = int(np_), int(cin), int(cout), int(H), int(W), int(nc), int(taps)
     a.bias = _p(bias); a.f_group = int(f_group)
     a.x_sl, a.y_sl, a.r_sl = int(x_sl), int(y_sl), int(y_sl)
@@ -466,9 +472,11 @@ def conv_tangent(x_t, x_off, x_np, x_ci, x_px, weight, taps, y_t, y_np, y_co, y_
     # output and residual element crosses HBM once (4 bytes each)
     px_in = float(H) * W * nc * np_
     px = px_in * (0.5 if live else 1.0)                     # checkerboard output: half the output pixels (and residual reads), every input pixel
+    # seeded residual: + the seed K-step's 9 taps of one channel, + the panel's bytes instead of a residual's
     TIMER.wrap(f"conv_tangent_t{taps}_ci{cin}_co{cout}" + ("_primal" if fmode == F_SELF_RELU else "_primal_bwd" if pbwd else "_live" if live else ""),
-               2.0 * cin * cout * taps * px,
-               4.0 * (px_in * cin + px * (cout + (cout if res_t is not None else 0))), launch)
+               2.0 * (cin + (1 if seed is not None else 0)) * cout * taps * px,
+               4.0 * (px_in * cin + px * (cout + (cout if res_t is not None else 0))
+                      + (float(seed["np"]) * np_ if seed is not None else 0.0)), launch)
 
 
 def _conv_tangent_head(lib, a, x_t, x_off, x_np, x_ci, x_px, weight, taps, y_t, y_np, y_co, y_px, np_, cin, cout, H, W, nc, fmode, f,
@@ -1631,6 +1639,10 @@ PROBE_FRONT_SHAPES = {(28, 28, 1)}
 
 PROBE_CLASSES = 13
 
+#: evaluation, couplers that take the probe front, two or more residual blocks: h_0 = conv0(mask . v) is never written -- block 0's
+#: conv2, its only reader, forms it from a one-channel seed panel in one extra K-step (False: the thin launch and a residual read)
+SEED_RESIDUAL = True
+
 
 def probe_plan(mask):
     """Host plan of the probe front for a coupler whose network reads ``mask . v``; ``mask`` (cin, H, W) array, != 0 = an input row.
@@ -1682,6 +1694,61 @@ def probe_apply(R, r_np, r_px, T, t_off, t_np, t_c, t_px, cls, y, y_np, y_px, np
     # <= 13 cin FMAs per output element; u0 is written and R read once (counted whole: the live fraction is data)
     px = float(H) * W * np_
     TIMER.wrap(f"probe_apply_ci{cin}", 2.0 * PROBE_CLASSES * cin * 64 * nc * px, 4.0 * px * 64 * (nc + 16 * ns), launch)
+
+
+def seed_plane(H, W):
+    """Floats per column plane of the seed panel: the zero-bordered image plus the one float a lane reads past its last row."""
+    return ((H + 2) * (W + 2) + 1 + 3) // 4 * 4
+
+
+def seed_panel(T, view, H, W):
+    """``cmf_seed_panel``: mask . v of a one-channel coupler input as (B, nc, seed_plane) fp32 with an exact-zero border -- what the
+    seeded-residual launch forms block 0's residual from.  ``T`` panel layout, read through ``view``."""
+    assert T.layout == "panel" and view.cin == 1
+    B, nc, HW, col = T.B, T.nc, H * W, seed_plane(H, W)
+    out = torch.empty(B * nc * col, dtype=torch.float32, device=T.data.device)
+    v = C.c_void_p(T.data.data_ptr() + 4 * int(view.chan_off * HW * nc))
+    launch = lambda: _lib.check(_lib.load().cmf_seed_panel(v, T.t_b, nc, _p(view.mask), _p(out), nc * col, col, B, H, W, nc, _stream()),
+                                "cmf_seed_panel")
+    TIMER = _timer()
+    if TIMER is None:
+        launch()
+    else:
+        TIMER.wrap("seed_panel", 0.0, 4.0 * B * nc * (col + HW), launch)
+    return dict(panel=out, np=nc * col, col=col)
+
+
+def seed_pack_host(w):
+    """Host restatement of ``cmf_pack_seed_weight`` (tests): ``w`` (64, 1, 3, 3) float32 array -> float32 (4, 64, 4), [co tile][lane =
+    16 kq + co % 16][j]: tap 3 kq + j of channel 16 tile + co % 16 for kq, j < 3, zero otherwise."""
+    w = np.asarray(w, dtype=np.float32).reshape(64, 9)
+    out = np.zeros((4, 64, 4), dtype=np.float32)
+    for kq in range(3):
+        for j in range(3):
+            out[:, 16 * kq:16 * kq + 16, j] = w[:, 3 * kq + j].reshape(4, 16)
+    return out
+
+
+def seed_panel_index(H, W):
+    """Host restatement of ``cmf_seed_panel``'s index map (tests): int array (seed_plane,), element q of a column plane = the image
+    pixel it holds, -1 on the zero border and in the padding."""
+    idx = np.full(seed_plane(H, W), -1, dtype=np.int64)
+    r, c = np.meshgrid(np.arange(H), np.arange(W), indexing="ij")
+    idx[((r + 1) * (W + 2) + c + 1).reshape(-1)] = (r * W + c).reshape(-1)
+    return idx
+
+
+def _seed_pack(conv0, dev):
+    """conv0's weight (64, 1, 3, 3) as the B operands of the seed K-step (``cmf_pack_seed_weight``): a function of the weight
+    alone, cached per parameter version like ``_probe_hidden``."""
+    def build():
+        w = conv0.weight.detach().contiguous()
+        assert tuple(w.shape) == (64, 1, 3, 3) and w.dtype == torch.float32
+        out = torch.empty(4096, dtype=torch.uint8, device=dev)
+        _lib.check(_lib.load().cmf_pack_seed_weight(_p(w), _p(out), _stream()), "cmf_pack_seed_weight")
+        return out
+
+    return DERIVED.get((id(conv0.weight), "seed-residual", str(dev)), [conv0.weight], build)
 
 
 def _probe_hidden(conv0, view, plan, H, W, hid, dev):
@@ -1743,10 +1810,6 @@ def net_tangent(net, T, view, acts, transpose_packs=False, save=None):
         # and was the 15k-cycle tail of every work item.  Only the kernels' strides know about it.
         hd = (hid * HW * nc, 16, hid * nc)                   # (np, chan, px)
         hsl = hid * 16                                       # slice stride
-        h = new(hid)
-        conv_tangent(T.data, view.chan_off * HW * nc, T.t_b, view.chan_step * HW * nc, nc, conv0.weight, 9, h.data, *hd,
-                     B, view.cin, hid, H, W, nc, fmode=F_RAW if view.mask is not None else F_NONE, f=view.mask, f_np=0,
-                     f_ci=HW, f_px=1, y_sl=hsl)
         fg = getattr(acts, "f_group", 1)                     # primal activations: (B,C,H,W) or (B/16,C,H,W,16)
         fs = dict(f_np=hid * HW * fg, f_ci=HW * fg, f_px=fg, f_group=fg)
         # relu' source of a hidden conv: float activations, or the bit mask the primal pass wrote (BitMask)
@@ -1768,6 +1831,15 @@ def net_tangent(net, T, view, acts, transpose_packs=False, save=None):
         probe = (PROBE_FRONT and plan is not None and save is None and fg == 1 and len(blocks) > 0 and hid == 64 and view.mask is not None
                  and T.layout == "panel" and nc % 16 == 0 and nc > 16 * plan["ns"] and (H, W, view.cin) in PROBE_FRONT_SHAPES
                  and cfg().tangent == "bf16x3" and _use_bf16x3(9, hid, W, False, H, hid))
+        # seeded residual: under the probe front h_0 has ONE reader, block 0's conv2 (as its residual), which can form it from mask . v
+        # itself -- the thin launch and h_0 go.  With one block the folded head reads h as its residual: that coupler keeps them.
+        seeded = SEED_RESIDUAL and probe and view.cin == 1 and len(blocks) >= 2 and isinstance(acts[1], BitMask)
+        h = None
+        if not seeded:
+            h = new(hid)
+            conv_tangent(T.data, view.chan_off * HW * nc, T.t_b, view.chan_step * HW * nc, nc, conv0.weight, 9, h.data, *hd,
+                         B, view.cin, hid, H, W, nc, fmode=F_RAW if view.mask is not None else F_NONE, f=view.mask, f_np=0,
+                         f_ci=HW, f_px=1, y_sl=hsl)
         for k, blk in enumerate(blocks):
             a_in, c1 = acts[2 * k], acts[2 * k + 1]
             ym = c1 if filt and isinstance(c1, BitMask) else None
@@ -1777,6 +1849,12 @@ def net_tangent(net, T, view, acts, transpose_packs=False, save=None):
             else:
                 conv_tangent(h.data, 0, *hd, blk.conv1.weight, 9, u.data, *hd, B, hid, hid, H, W, nc, x_sl=hsl, y_sl=hsl, **fk(a_in),
                              ymask=ym)
+            if seeded and k == 0:
+                sd = seed_panel(T, view, H, W)
+                conv_tangent(u.data, 0, *hd, blk.conv2.weight, 9, h2.data, *hd, B, hid, hid, H, W, nc, x_sl=hsl, y_sl=hsl,
+                             seed=dict(sd, pack=_seed_pack(conv0, dev)), **fk(c1))
+                h, h2 = h2, new(hid)
+                continue
             if fold and k + 1 == len(blocks):
                 # compact (checkerboard) or full output, the same arithmetic per pixel: CHECKERBOARD_TAIL stays bit-neutral
                 HWo = HW // 2 if compact else HW

@@ -142,6 +142,14 @@ typedef struct {
                                                 /* the float activation the 1x1 conv takes relu' from, (np, 64, H*W), always the FULL image */
   float* head_y; long long head_y_np, head_y_co, head_y_px;
                                                 /* yt: nc contiguous columns per (np, o, pixel); live != 0: compact pixels, row*(W/2) + col/2 */
+  const float* seed; long long seed_np, seed_col; const void* seed_w;
+                                                /* cmf_conv_tangent_bf16x3 only: SEEDED RESIDUAL.  seed != NULL: the launch is block 0's conv2 of a
+                                                   coupler network whose first conv has ONE input channel, and its residual h0 = conv0(mask . v)
+                                                   (networks.py:40-47, :62-79) is not read but formed: y = conv(F . x) + conv0(seed), the second
+                                                   term as one extra K-step per pixel on the fp32 MFMA (v_mfma_f32_16x16x4_f32).  seed is the panel cmf_seed_panel
+                                                   writes (element np*seed_np + col*seed_col + r*(W+2) + c of the zero-bordered image), seed_w the
+                                                   4 KiB pack of conv0's weight from cmf_pack_seed_weight.  Requires fmode CMF_F_RELU_BITS,
+                                                   cout == 64, W % 14 == 0, H % 2 == 0, r == NULL, no live / ymask / fo / bias; else CMF_EINVAL. */
 } cmf_conv_tangent_args;
 /* (A launch with taps == 9, cin <= 2, cout % 64 == 0, no residual / bias / output factor / mask_out and fmode NONE or RAW -- the
  * first conv of a coupler network, networks.py:40-47 -- is an HBM write stream and runs on a VALU kernel instead of the MFMA one:
@@ -162,6 +170,15 @@ int cmf_pack_weight_bf16x3(const float* w, void* out, int cout, int cin, long lo
  * [cout][cin][tap] = w[ci][co][8 - tap] (channels swapped, taps flipped: cmf_pack_weight's transpose for the split kernel) */
 int cmf_pack_weight_bf16x3_t(const float* w, void* out, int cout, int cin, int transpose, long long* out_bytes, void* stream);
 int cmf_conv_tangent_bf16x3(const cmf_conv_tangent_args* a, void* stream);
+/* The seeded residual's operands (cmf_conv_tangent_args.seed).  cmf_pack_seed_weight: w = conv0's weight [64][1][3][3] -> out, 4096
+ * bytes, 16-byte aligned: [co tile 4][lane 64][4] fp32, lane = 16 kq + co % 16, element j = tap 3 kq + j (kq, j < 3, else 0).
+ * cmf_seed_panel: out(np, col, r, c) = mask(r-1, c-1) * v(np, (r-1) W + (c-1), col) over the (H+2) x (W+2) image with an exact-zero
+ * border (and an exact 0 wherever mask == 0, whatever v holds there; mask NULL = all ones); v has nc contiguous columns per pixel
+ * (pixel stride v_px, sample stride v_np), out_col >= (H+2)(W+2) + 1 floats per column plane (the padding is zeroed), out_np >=
+ * nc out_col, nc % 16 == 0.                                                                                                      */
+int cmf_pack_seed_weight(const float* w, void* out, void* stream);
+int cmf_seed_panel(const float* v, long long v_np, long long v_px, const float* mask, float* out, long long out_np, long long out_col,
+                   int np, int H, int W, int nc, void* stream);
 
 /* Probe front of a checkerboard ResNet coupler's tangent network (evaluation; csrc/probe_front.hip).  The network's first conv
  * (cin <= 2 -> 64, networks.py:40-47, input mask . v: acl.py:48-52) and block 0's conv1 (64 -> 64, networks.py:62-79) are one linear
