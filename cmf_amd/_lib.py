@@ -32,7 +32,8 @@ class ConvTangentArgs(C.Structure):
                 ("ymask", _fp), ("ymask_np", _ll),
                 ("head_w", _fp), ("head_cout", _i), ("head_a", _fp), ("head_a_np", _ll), ("head_a_c", _ll), ("head_a_px", _ll),
                 ("head_y", _fp), ("head_y_np", _ll), ("head_y_co", _ll), ("head_y_px", _ll),
-                ("seed", _fp), ("seed_np", _ll), ("seed_col", _ll), ("seed_w", _fp)]
+                ("seed", _fp), ("seed_np", _ll), ("seed_col", _ll), ("seed_w", _fp),
+                ("block_w1", _fp), ("block_m1", _fp), ("block_m1_np", _ll)]
 
 
 class ConvPrimalArgs(C.Structure):
@@ -78,6 +79,7 @@ SIGNATURES = {
     "cmf_probe_apply": (_i, [C.POINTER(ProbeApplyArgs), _fp]),
     "cmf_pack_seed_weight": (_i, [_fp, _fp, _fp]),
     "cmf_seed_panel": (_i, [_fp, _ll, _ll, _fp, _fp, _ll, _ll, _i, _i, _i, _i, _fp]),
+    "cmf_pack_block_weight": (_i, [_fp, _fp, C.POINTER(_ll), _fp]),
     "cmf_pack_weight_f16x3": (_i, [_fp, _fp, _i, _i, _i, C.POINTER(_ll), _fp]),
     "cmf_conv_tangent_f16x3": (_i, [C.POINTER(ConvTangentArgs), _fp]),
     "cmf_conv_tangent_f16x3_item": (_i, [C.POINTER(ConvTangentArgs), _i, _fp]),

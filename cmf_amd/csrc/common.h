@@ -39,6 +39,8 @@ __device__ __forceinline__ float block_sum(float v, float* red) {
 
 // conv_head.hip: the folded head (last hidden conv + 1x1 output conv) behind cmf_conv_tangent_bf16x3; validates its own arguments
 int cmf_conv_head(const cmf_conv_tangent_args& a, hipStream_t s);
+// conv_block_head.hip: the folded block (last block's conv1 + conv2 + 1x1 conv), cmf_conv_head's dispatch target when a.block_w1 is set
+int cmf_conv_block_head(const cmf_conv_tangent_args& a, hipStream_t s);
 
 // head_wide.hip: the Jacobian head for 128 < nc <= 512 (d <= 512); dispatch targets of the C entry points, arguments validated there
 int cmf_wide_gram_cholesky(const float* t, long long t_b, long long t_r, int n_rows, int d, int B, float* jtj, float* logdet,

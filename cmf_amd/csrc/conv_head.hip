@@ -221,6 +221,7 @@ int launch(const cmf_conv_tangent_args& a, hipStream_t s) {
 
 // dispatch target of cmf_conv_tangent_bf16x3 (a.head_w != NULL); validates everything it relies on
 int cmf_conv_head(const cmf_conv_tangent_args& a, hipStream_t s) {
+  if (a.block_w1) return cmf_conv_block_head(a, s);             // folded block: conv1 of the last block taken in as well (conv_block_head.hip)
   if (!a.x || !a.w || !a.f || !a.r || !a.head_w || !a.head_a || !a.head_y) return CMF_EINVAL;
   if (a.fmode != CMF_F_RELU_BITS || a.taps != 9 || a.cin != HID || a.cout != HID) return CMF_EINVAL;
   if (a.head_cout < 1 || a.head_cout > 8 || a.np <= 0 || a.H <= 0 || a.W <= 0 || a.nc <= 0 || a.nc % 16) return CMF_EINVAL;

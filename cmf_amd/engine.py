@@ -402,7 +402,10 @@ def conv_tangent(x_t, x_off, x_np, x_ci, x_px, weight, taps, y_t, y_np, y_co, y_
     ``head`` = dict(weight=<the 1x1 conv's weight (cout', 64, 1, 1)>, act=<float activation (np, 64, H, W) it takes relu' from>):
     FOLDED HEAD (csrc/conv_head.hip) -- this launch is a coupler network's last hidden conv AND the 1x1 conv behind it; ``y_t`` and
     its strides then describe the 1x1 conv's output (np, cout', pixels, nc) (compact pixels under ``live``), ``res_t`` the block's
-    input h (slice-major like x, required), ``weight`` goes in raw, and the factor must be a BitMask's.
+    input h (slice-major like x, required), ``weight`` goes in raw, and the factor must be a BitMask's.  With a further entry
+    ``conv1=dict(weight=<the block's conv1 weight>, mask=<BitMask between conv1 and conv2>)``: FOLDED BLOCK
+    (csrc/conv_block_head.hip) -- the launch is the block's conv1 as well; ``x_t`` is then the block's input h (its own residual, no
+    ``res_t``) and the factor the BitMask of the activation in front of conv1.
     ``seed`` = dict(panel=, np=, col=, pack=) (``seed_panel`` / ``_seed_pack``): SEEDED RESIDUAL -- the launch is block 0's conv2 and
     forms its residual conv0(mask . v) itself from the one-channel seed panel; no ``res_t``, the factor must be a BitMask's."""
     lib = _lib.load()
@@ -492,6 +495,11 @@ def _conv_tangent_head(lib, a, x_t, x_off, x_np, x_ci, x_px, weight, taps, y_t, 
     a.r = None if res_t is None else C.c_void_p(res_t.data_ptr() + 4 * int(res_off))
     a.r_np, a.r_co, a.r_px, a.r_sl = int(x_np if res_np is None else res_np), int(x_ci), int(x_px), int(x_sl)
     a.np, a.cin, a.cout, a.H, a.W, a.nc, a.taps, a.live = int(np_), int(cin), int(cout), int(H), int(W), int(nc), int(taps), int(live)
+    blk = head.get("conv1")
+    if blk is not None:                                     # folded block: x is h, f its mask; conv1's pack and the mask behind it
+        assert res_t is None and isinstance(blk["mask"], BitMask), "the folded block reads h as x and takes relu'(c1) from a BitMask"
+        a.block_w1 = _p(_block_pack(blk["weight"], x_t.device))
+        a.block_m1, a.block_m1_np = _p(blk["mask"].data), int(blk["mask"].np_bytes)
     a.head_w, a.head_cout = _p(wf), hc
     a.head_a = _p(act); a.head_a_np, a.head_a_c, a.head_a_px = int(cin) * H * W, H * W, 1
     a.head_y = C.c_void_p(y_t.data_ptr() + 4 * int(y_off)); a.head_y_np, a.head_y_co, a.head_y_px = int(y_np), int(y_co), int(y_px)
@@ -502,6 +510,12 @@ def _conv_tangent_head(lib, a, x_t, x_off, x_np, x_ci, x_px, weight, taps, y_t, 
     # what the launch executes: per output pixel hc * 64 * 576 FMAs for E, then hc * 640 per column; u crosses HBM once (counted
     # whole: the live fraction is data), h at the output pixels, the activation and yt
     px_out = float(H) * W * np_ * (0.5 if live else 1.0)
+    if blk is not None:
+        # folded block: + the coefficient build (9 hc rows x 64 x 576 per output pixel, three bf16 products each), the apply's hc *
+        # 1600 FMAs per column; h crosses HBM once, the two bit masks, the activation and yt
+        return TIMER.wrap(f"conv_tangent_t{taps}_ci{cin}_co{cout}" + ("_live" if live else ""),
+                          2.0 * hc * px_out * (cin * taps * cout + 3 * taps * cin * taps * cout + 25 * cout * nc),
+                          4.0 * (float(H) * W * np_ * (nc * cin + 4) + px_out * (cout + nc * hc)), launch)
     TIMER.wrap(f"conv_tangent_t{taps}_ci{cin}_co{cout}" + ("_live" if live else ""),
                2.0 * hc * px_out * (cin * taps * cout + (cin * taps + cout) * nc),
                4.0 * (float(H) * W * np_ * nc * cin + px_out * (nc * cout + cout + nc * hc)), launch)
@@ -1630,6 +1644,13 @@ SKIP_DEAD_ROWS = True
 FOLD_HEAD = True
 
 
+#: evaluation, couplers that take the folded head, two or more residual blocks: the LAST block's conv1 goes into the folded launch
+#: too (csrc/conv_block_head.hip) -- conv1's output is never formed, its launch goes (False: conv1 launch + folded head)
+FOLD_BLOCK = True
+
+#: (H, W, cout) at which the folded block beat today's pair of launches by more than 3 x the run-to-run spread (profiles/fold_block.txt)
+FOLD_BLOCK_SHAPES = ((28, 28, 2),)
+
 #: evaluation, split-precision tangents on 64-channel checkerboard couplers: block 0's conv1 runs on one probe column per input
 #: class (13 per input channel) and csrc/probe_front.hip applies the responses to the real columns (False: conv1 on every column)
 PROBE_FRONT = True
@@ -1751,6 +1772,21 @@ def _seed_pack(conv0, dev):
     return DERIVED.get((id(conv0.weight), "seed-residual", str(dev)), [conv0.weight], build)
 
 
+def _block_pack(weight, dev):
+    """The last block's conv1 weight (64, 64, 3, 3) as the pre-split B fragments of the folded block's coefficient build
+    (``cmf_pack_block_weight``): a function of the weight alone, cached per parameter version like ``_seed_pack``."""
+    def build():
+        w = weight.detach().contiguous()
+        assert tuple(w.shape) == (64, 64, 3, 3) and w.dtype == torch.float32
+        n = C.c_longlong(0)
+        _lib.check(_lib.load().cmf_pack_block_weight(None, None, C.byref(n), None), "pack size")
+        out = torch.empty(n.value, dtype=torch.uint8, device=dev)
+        _lib.check(_lib.load().cmf_pack_block_weight(_p(w), _p(out), None, _stream()), "cmf_pack_block_weight")
+        return out
+
+    return DERIVED.get((id(weight), "fold-block", str(dev)), [weight], build)
+
+
 def _probe_hidden(conv0, view, plan, H, W, hid, dev):
     """conv0's tangent of the probe columns, (1, HW, ns, hid, 16) slice-major: a function of conv0's weight and the mask alone, so it is
     computed for ONE sample per parameter version (the thin kernel's arithmetic per element does not depend on the batch) and block
@@ -1795,7 +1831,9 @@ def net_tangent(net, T, view, acts, transpose_packs=False, save=None):
     block's conv2, through relu'(c1) -- so when that reader is such a launch, conv1 gets c1's mask as its store filter and leaves
     those rows unwritten (they hold whatever the buffer held).  The invariant: *a tensor with unwritten rows is only ever read by a
     launch that does not fetch those rows*.  Training (``save``) keeps full stores: ``net_cotangent`` and the weight gradients read
-    the saved ``u``."""
+    the saved ``u``.
+    Folded block (``FOLD_BLOCK``, shapes in ``FOLD_BLOCK_SHAPES``): where the folded head runs and the network has two or more
+    blocks, the last block issues no conv1 launch and no ``u``: one launch takes ``h_{K-1}`` to the network's output."""
     geo, B, nc, dev = view.geom, T.B, T.nc, T.data.device
     if save is not None:
         save.append(_view_rows(T, view))
@@ -1825,6 +1863,11 @@ def net_tangent(net, T, view, acts, transpose_packs=False, save=None):
         # take under CHECKERBOARD_TAIL = False exists to keep that off-switch bit-neutral: it is not a speed claim.)
         fold = (FOLD_HEAD and view.live is not None and save is None and fg == 1 and len(blocks) > 0 and hid == 64 and cout <= 8 and nc % 16 == 0
                 and isinstance(acts[2 * len(blocks) - 1], BitMask) and _use_bf16x3(9, hid, W, False, H, hid))
+        # folded block: the last block's conv1 goes into the folded launch as well (csrc/conv_block_head.hip); block 0 belongs to the
+        # probe front and the seeded residual
+        nb = len(blocks)
+        fold_block = (FOLD_BLOCK and fold and nb >= 2 and isinstance(acts[2 * nb - 2], BitMask) and isinstance(acts[2 * nb - 1], BitMask)
+                      and (H, W, cout) in FOLD_BLOCK_SHAPES)
         # probe front (csrc/probe_front.hip): block 0's conv1 on the plan's probe columns instead of all nc, then the apply kernel.
         # Only u_0 changes producer: h_0 on every column is still the thin kernel's (block 0's conv2 reads it as its residual).
         plan = getattr(view, "probe", None)
@@ -1843,6 +1886,16 @@ def net_tangent(net, T, view, acts, transpose_packs=False, save=None):
         for k, blk in enumerate(blocks):
             a_in, c1 = acts[2 * k], acts[2 * k + 1]
             ym = c1 if filt and isinstance(c1, BitMask) else None
+            if fold_block and k + 1 == nb:
+                # no conv1 launch, no u: one launch from h_{K-1} to yt (compact or full, the same arithmetic per pixel)
+                HWo = HW // 2 if compact else HW
+                yt = Tangent(B, cout * HWo, nc, "panel", dev)
+                conv_tangent(h.data, 0, *hd, blk.conv2.weight, 9, yt.data, cout * HWo * nc, HWo * nc, nc, B, hid, hid, H, W, nc,
+                             x_sl=hsl, live=view.live["parity"] if compact else 0,
+                             head=dict(weight=convf.weight, act=acts[-1], conv1=dict(weight=blk.conv1.weight, mask=c1)), **fk(a_in))
+                if compact:
+                    yt.compact = True
+                return yt
             if probe and k == 0:
                 # the responses go through h2's buffer: free until conv2 writes it, after the apply kernel has read them
                 probe_front(conv0, blk.conv1, T, view, plan, fk(a_in), ym, h2.data, u.data, H, W)

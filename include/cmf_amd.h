@@ -150,6 +150,19 @@ typedef struct {
                                                    writes (element np*seed_np + col*seed_col + r*(W+2) + c of the zero-bordered image), seed_w the
                                                    4 KiB pack of conv0's weight from cmf_pack_seed_weight.  Requires fmode CMF_F_RELU_BITS,
                                                    cout == 64, W % 14 == 0, H % 2 == 0, r == NULL, no live / ymask / fo / bias; else CMF_EINVAL. */
+  const void* block_w1; const void* block_m1; long long block_m1_np;
+                                                /* cmf_conv_tangent_bf16x3 only, with head_w: FOLDED BLOCK (csrc/conv_block_head.hip).  block_w1 != NULL
+                                                   takes the folded head one conv further: the launch is the last residual block's conv1 AND its
+                                                   conv2 (with the residual) AND the 1x1 output conv, and forms neither conv1's output nor the block's:
+                                                     yt(np, o, p, :) = sum_c G(o,c,p) x(np, c, p, :) + sum_{d in 5x5, c} K(o,p,d,c) F(np, c, p+d) x(np, c, p+d, :)
+                                                     K(o,p,d,c) = sum_{t2 + t1 = d} sum_ci E(o,p,t2,ci) [block_m1(np, ci, p+t2)] W1[ci][c][t1]
+                                                   with G and E as in the folded head.  WHICH IS WHICH: x is now the block's INPUT h (slice-major, also
+                                                   the residual: r must be NULL or x) and f / f_np the bit mask of ITS relu' (the activation in front
+                                                   of conv1); block_m1 / block_m1_np (bytes) is the bit mask between conv1 and conv2 (what f is for the
+                                                   folded head), same CMF_F_RELU_BITS layout; w stays conv2's RAW weight; block_w1 is conv1's weight as
+                                                   packed by cmf_pack_block_weight.  K is built from split bf16 products (hi*hi + hi*lo + lo*hi, fp32
+                                                   accumulation), everything else in fp32 FMAs.  A row of x is fetched only where F is set (at d = 0:
+                                                   F or head_a > 0).  Other requirements as for the folded head; else CMF_EINVAL.              */
 } cmf_conv_tangent_args;
 /* (A launch with taps == 9, cin <= 2, cout % 64 == 0, no residual / bias / output factor / mask_out and fmode NONE or RAW -- the
  * first conv of a coupler network, networks.py:40-47 -- is an HBM write stream and runs on a VALU kernel instead of the MFMA one:
@@ -177,6 +190,9 @@ int cmf_conv_tangent_bf16x3(const cmf_conv_tangent_args* a, void* stream);
  * (pixel stride v_px, sample stride v_np), out_col >= (H+2)(W+2) + 1 floats per column plane (the padding is zeroed), out_np >=
  * nc out_col, nc % 16 == 0.                                                                                                      */
 int cmf_pack_seed_weight(const float* w, void* out, void* stream);
+/* The folded block's W1 operand (cmf_conv_tangent_args.block_w1): w = conv1's weight [64][64][3][3] -> out (16-byte aligned), split into
+ * bf16 hi / lo halves and laid out as the B fragments of v_mfma_f32_16x16x32_bf16.  out == NULL: size query in bytes through *out_bytes. */
+int cmf_pack_block_weight(const float* w, void* out, long long* out_bytes, void* stream);
 int cmf_seed_panel(const float* v, long long v_np, long long v_px, const float* mask, float* out, long long out_np, long long out_col,
                    int np, int H, int W, int nc, void* stream);
 
