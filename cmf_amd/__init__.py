@@ -7,6 +7,7 @@ Public surface mirrors the reference for this path:
 """
 from .densities import PrecisionGuard
 from .factory import get_density
+from .geodesic import ManifoldGeodesic
 from .metric_spectrum import MetricSpectrum, effective_rank
 from .metric_stats import MetricStatistics
 from .projection import ManifoldProjector
@@ -15,4 +16,4 @@ from .schemas import DATA_SHAPES, get_config, get_schema
 
 __all__ = ["get_density", "get_config", "get_schema", "DATA_SHAPES", "get_non_square_train_metrics",
            "get_non_square_parameters", "PrecisionGuard", "MetricStatistics", "MetricSpectrum", "effective_rank",
-           "ManifoldProjector"]
+           "ManifoldProjector", "ManifoldGeodesic"]

@@ -1053,6 +1053,151 @@ def gauss_newton_step(T, jtj, x, xhat, damping):
     return r
 
 
+#: widest Jacobian ``cross_gram`` / ``curve_step`` take (csrc/curve_step.hip: the elimination window of a curve lives in LDS up to
+#: d = 64 and in a workspace slice up to d = 128)
+GEODESIC_MAX_WIDTH = 128
+
+
+class CurveStepResult:
+    """Outputs of ``curve_step`` (all on the device, float64 unless noted) for curves of P points, N = P - 1 segments and M = P - 2
+    interior points: ``grad`` and ``delta`` (curves, M, d), ``stats`` (curves, 4) = [sum_i ||r_i||^2, g^T delta, delta^T H delta,
+    max |g|], ``seg2`` (curves, N) = ||r_i||^2, ``info`` (curves,) int32 (0 ok, 1 non-positive pivot: delta and stats[:, 1:3] NaN,
+    2 non-finite input: everything NaN)."""
+    __slots__ = ("grad", "delta", "stats", "seg2", "info")
+
+
+def _curve_points(xhat, points):
+    """The checks ``curve_step`` and ``curve_energy`` share; returns (curves, elements per point)."""
+    if not isinstance(xhat, torch.Tensor) or not xhat.is_cuda:
+        raise ValueError(f"xhat must be on the GPU, got {getattr(xhat, 'device', type(xhat).__name__)} (there is no CPU fallback)")
+    if xhat.dtype != torch.float32:
+        raise ValueError(f"xhat must be float32, got {xhat.dtype}")
+    if xhat.dim() < 2 or not xhat.is_contiguous():
+        raise ValueError(f"xhat must be a contiguous (curves * points, ...) tensor, got {tuple(xhat.shape)}"
+                         f"{'' if xhat.is_contiguous() else ' (not contiguous)'}")
+    points = int(points)
+    if points < 3 or xhat.shape[0] % points:
+        raise ValueError(f"points = {points}: a curve needs points >= 3, and the {xhat.shape[0]} samples of xhat must be whole curves")
+    n = int(np.prod(xhat.shape[1:]))
+    if n < 1:
+        raise ValueError(f"xhat must have at least one element per point, got {tuple(xhat.shape)}")
+    return xhat.shape[0] // points, n
+
+
+def _curve_tangent(T, d, points):
+    if not isinstance(T, Tangent):
+        raise ValueError(f"T must be an engine.Tangent, got {type(T).__name__}")
+    if not T.data.is_cuda:
+        raise ValueError(f"T must be on the GPU, got {T.data.device} (there is no CPU fallback)")
+    if not 1 <= int(d) <= GEODESIC_MAX_WIDTH:
+        raise ValueError(f"d = {int(d)}: the curve kernels support 1 <= d <= {GEODESIC_MAX_WIDTH}")
+    if int(points) < 3 or T.B % int(points):
+        raise ValueError(f"points = {int(points)}: a curve needs points >= 3, and the {T.B} samples of T must be whole curves")
+    if T.nc % 16 or T.nc < d or T.nc > GEODESIC_MAX_WIDTH:
+        raise ValueError(f"T (nc = {T.nc}) must hold d = {int(d)} <= nc <= {GEODESIC_MAX_WIDTH} columns, nc % 16 == 0")
+
+
+def cross_gram(T, d, points):
+    """The cross-Gram matrices of neighbouring interior points of curve-major curves: ``T`` holds curves * points
+    samples, the result is (curves, points - 3, d, d) float32 with [c, i - 1] = J_{c,i}^T J_{c,i+1}, i = 1 .. points - 3.  fp32 MFMA,
+    deterministic per pair; one launch, no synchronisation."""
+    _curve_tangent(T, d, points)
+    d, points = int(d), int(points)
+    curves = T.B // points
+    out = torch.empty(curves, points - 3, d, d, dtype=torch.float32, device=T.data.device)
+    if out.numel() == 0:
+        return out
+    launch = lambda: _lib.check(_lib.load().cmf_cross_gram(_p(T.data), T.t_b, T.t_r, T.N, T.nc, d, points, curves, _p(out), _stream()),
+                                "cmf_cross_gram")
+    TIMER = _timer()
+    if TIMER is None:
+        launch()
+    else:                                          # 2 D d^2 FLOP per pair; both panels in, the block out
+        pairs = curves * (points - 3)
+        TIMER.wrap("cross_gram", pairs * 2.0 * T.N * d * d, 4.0 * pairs * (2 * T.N * T.nc + d * d), launch)
+    return out
+
+
+def curve_energy(xhat, points):
+    """||xhat_{i+1} - xhat_i||^2 per segment of curve-major curves in float64, by the energy-only mode of the curve step kernel (the
+    same arithmetic, bit for bit, as ``curve_step(...).seg2`` and ``.stats[:, 0]``): returns (seg2 (curves, points - 1) float64, their
+    sum (curves,) float64, info (curves,) int32 -- 0, or 2 with NaN outputs for a non-finite input).  One launch, no
+    synchronisation."""
+    curves, n = _curve_points(xhat, points)
+    points = int(points)
+    seg2 = torch.empty(curves, points - 1, dtype=torch.float64, device=xhat.device)
+    stats = torch.empty(curves, 4, dtype=torch.float64, device=xhat.device)
+    info = torch.empty(curves, dtype=torch.int32, device=xhat.device)
+    if curves == 0:
+        return seg2, stats[:, 0], info
+    launch = lambda: _lib.check(_lib.load().cmf_curve_step(None, 0, 0, n, 0, 0, points, curves, None, None, _p(xhat), None, None, None,
+                                                           _p(stats), _p(seg2), _p(info), None, 0, _stream()), "cmf_curve_step")
+    TIMER = _timer()
+    if TIMER is None:
+        launch()
+    else:                                          # a subtraction, a multiply and an add per element and segment; xhat in twice
+        TIMER.wrap("curve_energy", 3.0 * curves * (points - 1) * n, curves * (8.0 * (points - 1) * n + 8.0 * points + 4.0), launch)
+    return seg2, stats[:, 0], info
+
+
+def curve_step(T, jtj, cross, xhat, points, damping):
+    """One damped Gauss-Newton step per curve: from the Jacobian stack ``T`` of a decode sweep over curves * points
+    curve-major samples, its Gram matrices ``jtj`` (curves * points, d, d) float32 (one ``gram_cholesky`` attempt; the lower triangles
+    of the interior points are read), ``cross`` of ``cross_gram``, the decoded points ``xhat`` (curves * points, ...) float32 and
+    ``damping`` (curves,) float64 >= 0, in float64: the gradient of the interior points and delta = (H + damping diag H)^-1 grad on
+    the block tridiagonal Gauss-Newton matrix H.  Returns a ``CurveStepResult``.  Deterministic per curve; one launch, no
+    synchronisation."""
+    curves, n = _curve_points(xhat, points)
+    points, dev = int(points), xhat.device
+    for name, v in (("jtj", jtj), ("cross", cross)):
+        if not isinstance(v, torch.Tensor) or not v.is_cuda:
+            raise ValueError(f"{name} must be on the GPU, got {getattr(v, 'device', type(v).__name__)} (there is no CPU fallback)")
+        if v.dtype != torch.float32:
+            raise ValueError(f"{name} must be float32, got {v.dtype}")
+    if jtj.dim() != 3 or jtj.shape[1] != jtj.shape[2] or not jtj.is_contiguous():
+        raise ValueError(f"jtj must be a contiguous (curves * points, d, d) tensor, got {tuple(jtj.shape)}"
+                         f"{'' if jtj.is_contiguous() else ' (not contiguous)'}")
+    d = jtj.shape[1]
+    _curve_tangent(T, d, points)
+    if cross.shape != (curves, points - 3, d, d) or not cross.is_contiguous():
+        raise ValueError(f"cross must be a contiguous ({curves}, {points - 3}, {d}, {d}) tensor, got {tuple(cross.shape)}"
+                         f"{'' if cross.is_contiguous() else ' (not contiguous)'}")
+    if T.B != curves * points or T.N != n or jtj.shape[0] != T.B or T.data.device != dev or jtj.device != dev or cross.device != dev:
+        raise ValueError(f"T (B = {T.B}, N = {T.N}, nc = {T.nc}) on {T.data.device} must hold d = {d} <= nc columns, nc % 16 == 0, "
+                         f"for the {curves * points} samples of {n} elements of xhat on {dev}, like jtj {tuple(jtj.shape)} on "
+                         f"{jtj.device} and cross on {cross.device}")
+    if not isinstance(damping, torch.Tensor) or damping.dtype != torch.float64 or damping.device != dev or \
+            damping.shape != (curves,) or not damping.is_contiguous():
+        raise ValueError(f"damping must be {curves} contiguous float64 values on {dev}")
+    r = CurveStepResult()
+    r.grad = torch.empty(curves, points - 2, d, dtype=torch.float64, device=dev)
+    r.delta = torch.empty(curves, points - 2, d, dtype=torch.float64, device=dev)
+    r.stats = torch.empty(curves, 4, dtype=torch.float64, device=dev)
+    r.seg2 = torch.empty(curves, points - 1, dtype=torch.float64, device=dev)
+    r.info = torch.empty(curves, dtype=torch.int32, device=dev)
+    if curves == 0:
+        return r
+    lib = _lib.load()
+    need = lib.cmf_curve_step_ws(d, points, curves)
+    _lib.check(min(need, 0), "cmf_curve_step_ws")
+    ws = torch.empty(need, dtype=torch.float64, device=dev)
+    launch = lambda: _lib.check(lib.cmf_curve_step(_p(T.data), T.t_b, T.t_r, n, T.nc, d, points, curves, _p(jtj),
+                                                   _p(cross) if cross.numel() else None, _p(xhat), _p(damping), _p(r.grad), _p(r.delta),
+                                                   _p(r.stats), _p(r.seg2), _p(r.info), _p(ws), need, _stream()), "cmf_curve_step")
+    TIMER = _timer()
+    if TIMER is None:
+        launch()
+    else:
+        # float64 per curve: J^T s 2 D d per interior point, the block elimination 7 d^3 / 3 per block (d columns on a 2 d window)
+        # with the substitutions 6 d^2, the segments 3 D, the forms 5 d^2; bytes: the live quarter-rows of J, three rows of xhat per
+        # point, jtj and cross three times, the eliminated columns out and in, the outputs
+        M, ncl = points - 2, min(T.nc, -(-d // 4) * 4)
+        TIMER.wrap("curve_step", curves * (M * (2.0 * n * d + 7.0 * d ** 3 / 3.0 + 11.0 * d * d) + 3.0 * (points - 1) * n),
+                   curves * (M * (4.0 * n * ncl + 12.0 * n + 20.0 * d * d + 16.0 * (2 * d + 1) * d + 16.0 * d)
+                             + 8.0 * points * n + 8.0 * points + 36.0), launch)
+    return r
+
+
 def gram_backward(T, jtj, g_logdet=None, g_l1off=None, g_l1diag=None):
     """Cotangent of the Jacobian stack T for a loss with d/d logdet = g_logdet, d/d l1_off = g_l1off, d/d l1_diag =
     g_l1diag (each (B,) or None): what autograd yields through non_square.py:307-308, :280-294, :87-100."""

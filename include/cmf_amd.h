@@ -442,6 +442,41 @@ int cmf_gram_spectrum(const float* jtj, int d, int B, double* eigenvalues, doubl
 int cmf_gauss_newton_step(const float* t, long long t_b, long long t_r, int n_rows, int nc, int d, int B,
                           const float* jtj, const float* x, const float* xhat, const double* damping,
                           double* grad, double* delta, double* stats, int* info, void* stream);
+/* One damped Gauss-Newton step on whole discretised curves with fixed end points.  A curve has `points` = P >= 3
+ * points, N = P - 1 segments and M = P - 2 interior points; samples are curve-major: point i of curve c is sample c P + i of the
+ * Jacobian stack t, of jtj and of xhat.  With r_i = xhat_{i+1} - xhat_i:
+ *   g_i = J_i^T (xhat_{i-1} + xhat_{i+1} - 2 xhat_i),  H block tridiagonal with H_ii = 2 J_i^T J_i, H_{i,i+1} = -C_i,
+ *   C_i = J_i^T J_{i+1},  A = H + damping[c] diag(H),  delta = A^-1 g  over the interior points i = 1 .. M.
+ *
+ * cmf_cross_gram: cross [curves][P - 3][d][d] float32, cross[c][i - 1][a][b] = sum_r J_{c,i}[r][a] J_{c,i+1}[r][b] for i = 1 ..
+ * P - 3, the whole (unsymmetric) block, by fp32 MFMA with fp32 accumulation.  With P == 3 nothing is written and cross may be
+ * NULL.  t, t_b, t_r, n_rows, nc as cmf_gram_cholesky takes them, nc <= 128; columns d .. nc - 1 are padding whose contents
+ * influence no output.  The order of every sum is a function of (n_rows, nc, d) alone -- not of the column's position, of the
+ * pair, of `curves` or of completion order: two bit-identical columns of J give bit-identical rows of cross.  A non-finite input
+ * reaches its own pair's block only.
+ *
+ * cmf_curve_step, per curve in float64:
+ *   jtj [curves P][d][d] float32 as ONE cmf_gram_cholesky attempt leaves it: the lower triangles of the interior points are read,
+ *     nothing is written; cross as above; xhat [curves P][n_rows] float32; damping [curves] float64, >= 0.
+ *   seg2 [curves][N] = ||r_i||^2;  grad, delta [curves][M][d];
+ *   stats [curves][4] = { sum_i ||r_i||^2, g^T delta, delta^T H delta, max |g| };
+ *   info [curves] int32: 0 ok; 1 a pivot of A was not positive and finite (delta, stats[1], stats[2] are NaN, the rest is valid);
+ *     2 a non-finite value in xhat, in the first d columns of an interior point's t or in the parts of jtj / cross that are read
+ *     (every output of the curve is NaN).
+ *   ws: caller-owned, 8-byte aligned, ws_doubles >= cmf_curve_step_ws(d, points, curves) doubles (CMF_EINVAL for arguments out of
+ *     range): the eliminated columns of every block and, for 64 < d, the elimination window, one slice per curve.
+ * Energy-only mode, t == NULL: only seg2, stats[c][0] and info[c] (0 or 2) are written -- the same bits as the full mode gives;
+ * the Jacobian arguments, jtj, cross, damping, grad, delta and ws are not looked at.
+ * A curve's outputs are a function of its own inputs and of (n_rows, nc, d, P) alone: no atomics, independent of `curves`, of the
+ * curve's position and of completion order, and they repeat bit for bit.
+ * 1 <= d <= 128, nc % 16 == 0, d <= nc, t_b and t_r >= nc and % 4 == 0, t 16-byte aligned, float64 pointers 8-byte aligned,
+ * n_rows, curves >= 1.  Anything else: CMF_EINVAL.  No allocation, no synchronisation.                                        */
+int cmf_cross_gram(const float* t, long long t_b, long long t_r, int n_rows, int nc, int d, int points, int curves, float* cross,
+                   void* stream);
+long long cmf_curve_step_ws(int d, int points, int curves);
+int cmf_curve_step(const float* t, long long t_b, long long t_r, int n_rows, int nc, int d, int points, int curves,
+                   const float* jtj, const float* cross, const float* xhat, const double* damping, double* grad, double* delta,
+                   double* stats, double* seg2, int* info, double* ws, long long ws_doubles, void* stream);
 /* Reverse of the head above for training (autograd through non_square.py:307-308, :280-294, :87-100):
  *   dt(b, r, :) = 2 * t(b, r, :) * (g_logdet[b] * jtj_b^-1 + g_l1off[b] * sign(jtj_b)[i != j]
  *                                   + g_l1diag[b] * sign(jtj_b)[i == j])
