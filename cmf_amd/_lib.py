@@ -11,6 +11,8 @@ LIB_PATH = os.path.join(_HERE, "libcmf_amd.so")
 
 F_NONE, F_RELU, F_TANH, F_RAW, F_SELF_RELU, F_RELU_BITS = 0, 1, 2, 3, 4, 5
 O_NONE, O_TANH, O_STANH = 0, 1, 2
+# cmf_gram_cholesky_family: 1 .. 8 = the LDS-staged kernel with that many 16-column tiles
+GRAM_INVALID, GRAM_RING64, GRAM_DIRECT128, GRAM_WIDE, GRAM_RING_LIMIT = 0, 64, 128, 512, 0x7fffff00
 
 _fp = C.c_void_p      # device pointers travel as integers (tensor.data_ptr())
 _ll = C.c_longlong
@@ -101,6 +103,7 @@ SIGNATURES = {
     "cmf_seed_tangent": (_i, [_fp, _ll, _ll, _fp, _i, _i, _fp, _i, _i, _i, _fp]),
     "cmf_gram_cholesky": (_i, [_fp, _ll, _ll, _i, _i, _i, _i, _fp, _fp, _fp, _fp, _fp, _fp, _fp]),
     "cmf_cholesky_retry": (_i, [_fp, _i, _i, _i, _f, _fp, _fp, _fp, _fp, _fp]),
+    "cmf_gram_cholesky_family": (_i, [_i, _i, _ll]),
     "cmf_gram_condition": (_i, [_fp, _fp, _i, _i, _f, _fp, _fp, _fp, _fp, _fp]),
     "cmf_metric_stats_ws": (_ll, [_i, _i, _i, _i]),
     "cmf_metric_stats_accumulate": (_i, [_fp, _i, _i, _i, _fp, _fp, _ll, _fp, _fp]),

@@ -634,36 +634,68 @@ int launch_gram(const float* t, long long t_b, long long t_r, int n_rows, int d,
 
 }  // namespace
 
+#ifndef CMF_DBG_GRAMPF
+#define CMF_DBG_GRAMPF 8                            // measured: 8 groups ahead beat 12 / 16 / 24 by 3 - 12 us at B = 512
+#endif
+#ifndef CMF_DBG_GRAM64_MIN_NC
+#define CMF_DBG_GRAM64_MIN_NC 32                    // measured (B = 512, D = 784): nc 48: 75.6 -> 40.4 us, nc 32: 51.4 -> 38.7 us;
+                                                    // nc 16 (tabular, B = 4096): the small-LDS staged kernel wins, 19.5 vs 51.9 us
+#endif
+
+// Which kernel cmf_gram_cholesky runs for a panel of n_rows rows of nc columns with row stride t_r (floats).  Host only.
+// The two ring kernels (gram_chol64_kernel, gram_chol_direct_kernel<8>) address one sample's panel with 32-bit BYTE offsets:
+// the descriptor range n_rows * t_r * 4, the wave-uniform offset of the next group, which runs PF groups past the last one the
+// wave consumes, the advance of one group, and the lane offset inside a group.  They are chosen only when the largest of these
+// -- the group offset after the last load, plus the largest lane offset and its 16 bytes -- stays below CMF_GRAM_RING_LIMIT,
+// computed here in 64 bits with the kernels' own group counts.  Everything else (feature-major tensors of large batches, long
+// row strides) runs the LDS-staged kernel, which addresses in 64 bits.
+extern "C" int cmf_gram_cholesky_family(int n_rows, int nc, long long t_r) {
+  if (n_rows <= 0 || nc <= 0 || nc % 16 || nc > 512 || t_r < nc || t_r % 4) return CMF_GRAM_INVALID;
+  if (nc > 128) return CMF_GRAM_WIDE;
+  constexpr long long PF = CMF_DBG_GRAMPF;
+  const long long row_bytes = t_r * 4, ngroups_all = ((long long)n_rows + 3) >> 2;
+  if (nc >= CMF_DBG_GRAM64_MIN_NC && nc <= 64) {
+    // gram_chol64_kernel: wave w takes the 4-row groups w, w + 4, ...; one load advances the offset by 16 rows; PF loads up
+    // front and PF per full round of the main loop.  Lane offset: row (wave * 4 + kq) <= 15 of the group, 16 bytes at column 4 cl.
+    const long long ng0 = (ngroups_all + 3) / 4;                       // wave 0 has the most groups
+    const long long loads = PF + PF * (ng0 / PF);
+    const long long top = loads * 16 * row_bytes + 15 * row_bytes + 15 * 16 + 16;
+    if (top < CMF_GRAM_RING_LIMIT) return CMF_GRAM_RING64;
+  } else if (nc == 128) {
+    // gram_chol_direct_kernel<8>: every wave walks all 4-row groups; PF loads up front, PF per round of the loop, which
+    // rounds the group count UP to a multiple of PF.  Lane offset: row kq <= 3, two 16-byte loads at column 8 cl.
+    const long long loads = PF + PF * ((ngroups_all + PF - 1) / PF);
+    const long long top = loads * 4 * row_bytes + 3 * row_bytes + 15 * 32 + 16 + 16;
+    if (top < CMF_GRAM_RING_LIMIT) return CMF_GRAM_DIRECT128;
+  }
+  return nc / 16;                                   // CMF_GRAM_STAGED1 ... CMF_GRAM_STAGED8 = NT of gram_chol_kernel<NT>
+}
+
 extern "C" int cmf_gram_cholesky(const float* t, long long t_b, long long t_r, int n_rows, int nc, int d, int B,
                                  float* jtj, float* logdet, float* l1_off, float* l1_diag, int* info, int* fail,
                                  void* stream) {
   if (!t || !jtj || !logdet || !l1_off || !l1_diag || !info || !fail) return CMF_EINVAL;
   if (n_rows <= 0 || B <= 0 || d <= 0 || d > nc || nc % 16 || nc > 512) return CMF_EINVAL;
   if ((t_b | t_r) % 4 || (uintptr_t)t % 16) return CMF_EINVAL;
+  const int family = cmf_gram_cholesky_family(n_rows, nc, t_r);
+  if (family == CMF_GRAM_INVALID) return CMF_EINVAL;
   hipStream_t s = (hipStream_t)stream;
   // A kernel node, not hipMemsetAsync: a captured 32-byte memset node replayed with garbage from the second
   // hipGraphLaunch on (ROCm 7.2, observed as pointer-like values in the flags), which silently armed every retry.
   hipLaunchKernelGGL(zero_flags_kernel, dim3(1), dim3(64), 0, s, fail);
   CMF_LAUNCH_CHECK();
-  if (nc > 128) return cmf_wide_gram_cholesky(t, t_b, t_r, n_rows, d, B, jtj, logdet, l1_off, l1_diag, info, fail, s);
 #ifdef CMF_DBG_GRAMOLD
-  if (nc == 64) return launch_gram_direct<4>(t, t_b, t_r, n_rows, d, B, jtj, logdet, l1_off, l1_diag, info, fail, s);
+  if (family == CMF_GRAM_RING64 && nc == 64)
+    return launch_gram_direct<4>(t, t_b, t_r, n_rows, d, B, jtj, logdet, l1_off, l1_diag, info, fail, s);
 #endif
-#ifndef CMF_DBG_GRAMPF
-#define CMF_DBG_GRAMPF 8                            // measured: 8 groups ahead beat 12 / 16 / 24 by 3 - 12 us at B = 512
-#endif
-  // nc <= 64: the d <= 64 kernel (narrower panels through lane masking).  The panel of one sample must fit the 32-bit byte
-  // offsets of its buffer descriptor (feature-major tensors of large batches do not: they keep the LDS-staged kernel)
-#ifndef CMF_DBG_GRAM64_MIN_NC
-#define CMF_DBG_GRAM64_MIN_NC 32                    // measured (B = 512, D = 784): nc 48: 75.6 -> 40.4 us, nc 32: 51.4 -> 38.7 us;
-                                                    // nc 16 (tabular, B = 4096): the small-LDS staged kernel wins, 19.5 vs 51.9 us
-#endif
-  if (nc >= CMF_DBG_GRAM64_MIN_NC && nc <= 64 && (long long)n_rows * t_r * 4 < 0x7fffff00LL)
-    return launch_gram64<CMF_DBG_GRAMPF>(t, t_b, t_r, n_rows, nc, d, B, jtj, logdet, l1_off, l1_diag, info, fail, s);
-  if (nc == 128) return launch_gram_direct<8>(t, t_b, t_r, n_rows, d, B, jtj, logdet, l1_off, l1_diag, info, fail, s);
 #define CMF_GRAM_CASE(N) \
   case N: return launch_gram<N>(t, t_b, t_r, n_rows, d, B, jtj, logdet, l1_off, l1_diag, info, fail, s);
-  switch (nc / 16) {
+  switch (family) {
+    case CMF_GRAM_WIDE: return cmf_wide_gram_cholesky(t, t_b, t_r, n_rows, d, B, jtj, logdet, l1_off, l1_diag, info, fail, s);
+    // nc 32 / 48 / 64: the d <= 64 kernel (narrower panels through lane masking)
+    case CMF_GRAM_RING64:
+      return launch_gram64<CMF_DBG_GRAMPF>(t, t_b, t_r, n_rows, nc, d, B, jtj, logdet, l1_off, l1_diag, info, fail, s);
+    case CMF_GRAM_DIRECT128: return launch_gram_direct<8>(t, t_b, t_r, n_rows, d, B, jtj, logdet, l1_off, l1_diag, info, fail, s);
     CMF_GRAM_CASE(1) CMF_GRAM_CASE(2) CMF_GRAM_CASE(3) CMF_GRAM_CASE(4)
     CMF_GRAM_CASE(5) CMF_GRAM_CASE(6) CMF_GRAM_CASE(7) CMF_GRAM_CASE(8)
   }

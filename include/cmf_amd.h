@@ -374,12 +374,29 @@ int cmf_seed_tangent(float* t, long long t_b, long long t_r, const int* col_of, 
  * jtj (in place) and refactorises.  The host may enqueue all retries without synchronising.
  * Widths: nc % 16 == 0, d <= nc <= 512 (cmf_cholesky_retry: d <= 512).  nc <= 128 keeps the whole matrix in LDS; 128 < nc runs
  * head_wide.hip (Gram on a (tile, sample) grid, blocked factorisation in global memory that restores jtj afterwards, so jtj is
- * exactly symmetric and intact on return).  Wider: CMF_EINVAL.                                                              */
+ * exactly symmetric and intact on return).  Wider: CMF_EINVAL.
+ * Layout contract: row r of sample b is the nc floats at t + b * t_b + r * t_r (t_r >= nc, t_b and t_r multiples of 4, t 16-byte
+ * aligned); nothing outside those nc floats of a row is read.  The padding columns d .. nc - 1 must hold ZEROS: the nc <= 64
+ * kernel sums |G_ij| over whole 4 x 4 register blocks and relies on the padding rows / columns of G being exact zeros.       */
 int cmf_gram_cholesky(const float* t, long long t_b, long long t_r, int n_rows, int nc, int d, int B,
                       float* jtj, float* logdet, float* l1_off, float* l1_diag, int* info, int* fail,
                       void* stream);
 int cmf_cholesky_retry(float* jtj, int d, int B, int attempt, float eps0, float* logdet, float* l1_diag,
                        int* info, int* fail, void* stream);
+/* Which kernel cmf_gram_cholesky runs for (n_rows, nc, t_r): a host-only query, no launch, no device access, and the function the
+ * dispatcher itself switches on.  CMF_GRAM_STAGED1 .. 8: the LDS-staged kernel with NT = nc / 16 column tiles (64-bit addressing);
+ * CMF_GRAM_RING64 (nc 32 / 48 / 64) and CMF_GRAM_DIRECT128 (nc 128): the kernels that stream the panel through a buffer
+ * descriptor with 32-bit byte offsets, chosen only when every offset they form -- the descriptor range n_rows * t_r * 4, the
+ * group offset the prefetch ring runs past the panel's end, the lane offset -- stays below CMF_GRAM_RING_LIMIT; CMF_GRAM_WIDE:
+ * head_wide.hip (nc > 128); CMF_GRAM_INVALID: n_rows <= 0, nc not a multiple of 16 in 16 .. 512, t_r < nc or t_r % 4 != 0.   */
+#define CMF_GRAM_INVALID   0
+#define CMF_GRAM_STAGED1   1
+#define CMF_GRAM_STAGED8   8
+#define CMF_GRAM_RING64    64
+#define CMF_GRAM_DIRECT128 128
+#define CMF_GRAM_WIDE      512
+#define CMF_GRAM_RING_LIMIT 0x7fffff00LL
+int cmf_gram_cholesky_family(int n_rows, int nc, long long t_r);
 /* Conditioning of the factorised Gram matrices (the precision guard of the no-grad log-density path):
  *   cond[b] = kappa_1(G_b) = ||G_b||_1 ||G_b^-1||_1 of the matrix cmf_gram_cholesky / cmf_cholesky_retry left in jtj (the
  *   jittered Gram whose log-det is reported), computed exactly in float64 (Cholesky, triangular inverse, |G^-1| column sums);
