@@ -224,13 +224,12 @@ class AffineCouplingBijection(Bijection):
             Tc = E.seed_tangent(T.B, T.N, sc["nc"], T.layout, sc["col_of"], sc["n"], c.x.device)
             YTc = E.net_tangent(self.net, Tc, view, c.acts)
             YT = E.expand_columns(YTc, T.nc, sc["colmap"])
-            YT.compact = getattr(YTc, "compact", False)
         if save:
             c.YT = YT
         self._acl_tangent(T, YT, c.x, c.y, c.g)
 
     def _acl_tangent(self, T, YT, z, y, g):
-        if getattr(YT, "compact", False):
+        if YT is not None and YT.compact:
             # checkerboard tail (engine.net_tangent): the network's tangent exists at the modified pixels only, stored compactly;
             # (s, g) are read through the same compact index maps
             cm = self.compact_maps(z.device)

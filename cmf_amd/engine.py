@@ -13,6 +13,7 @@ Layouts
 """
 import ctypes as C
 import threading
+from typing import NamedTuple
 
 import numpy as np
 import torch
@@ -184,8 +185,9 @@ def _shape_ok_bf16x3(taps, cin, W, transpose, H=None, cout=64):
 class Tangent:
     """A stack of Jacobian columns attached to a primal tensor of N elements per sample."""
 
-    def __init__(self, B, N, nc, layout, device, data=None):
+    def __init__(self, B, N, nc, layout, device, data=None, compact=False):
         self.B, self.N, self.nc, self.layout = int(B), int(N), int(nc), layout
+        self.compact = compact            # a checkerboard coupler network's output at its live pixels only (TangentPlan.compact)
         numel = self.B * self.N * self.nc
         self.data = data if data is not None else torch.empty(numel, dtype=torch.float32, device=device)
         assert self.data.numel() >= numel
@@ -629,7 +631,7 @@ def gather_tangent(T, idx, n_out):
 def expand_columns(T, nc_out, colmap):
     """A panel-layout tangent stack with ``nc_out`` column slots: column c = column ``colmap[c]`` of ``T`` (or zero where -1)."""
     assert T.layout == "panel"
-    out = Tangent(T.B, T.N, nc_out, "panel", T.data.device)
+    out = Tangent(T.B, T.N, nc_out, "panel", T.data.device, compact=T.compact)
     _lib.check(_lib.load().cmf_expand_columns(_p(T.data), T.nc, _p(out.data), int(nc_out), _p(colmap), T.B * T.N, _stream()),
                "cmf_expand_columns")
     return out
@@ -1778,36 +1780,19 @@ def _view_rows(T, view):
     return out
 
 
-#: checkerboard couplers: last hidden conv and 1x1 conv at the (1 - mask) pixels only (False: every pixel, rounds 1 - 4)
-CHECKERBOARD_TAIL = True
-
-#: evaluation: a residual block's conv1 does not store the rows of its output that conv2 will not fetch (False: every row)
-SKIP_DEAD_ROWS = True
-
-#: evaluation, split-precision tangents on 64-channel couplers: the last hidden conv and the 1x1 output conv run as ONE fp32 launch
-#: that never forms the 64 hidden channels (False: two launches and a gather of the last activation)
-FOLD_HEAD = True
-
-
-#: evaluation, couplers that take the folded head, two or more residual blocks: the LAST block's conv1 goes into the folded launch
-#: too (csrc/conv_block_head.hip) -- conv1's output is never formed, its launch goes (False: conv1 launch + folded head)
-FOLD_BLOCK = True
-
+#: Switches of the work-skipping forms of a ResNet coupler's tangent sweep: ``TangentPlan`` says what each form is, ``resnet_tangent_plan``
+#: reads them on every call.  False restores the launches the form replaced.
+CHECKERBOARD_TAIL = True          # TangentPlan.tail "live", TangentPlan.compact (False: every pixel, rounds 1 - 4)
+SKIP_DEAD_ROWS = True             # TangentPlan.filt
+FOLD_HEAD = True                  # TangentPlan.tail "head"
+FOLD_BLOCK = True                 # TangentPlan.tail "block"
+PROBE_FRONT = True                # TangentPlan.front "probe"
+SEED_RESIDUAL = True              # TangentPlan.front "seeded"
 #: (H, W, cout) at which the folded block beat today's pair of launches by more than 3 x the run-to-run spread (profiles/fold_block.txt)
 FOLD_BLOCK_SHAPES = ((28, 28, 2),)
-
-#: evaluation, split-precision tangents on 64-channel checkerboard couplers: block 0's conv1 runs on one probe column per input
-#: class (13 per input channel) and csrc/probe_front.hip applies the responses to the real columns (False: conv1 on every column)
-PROBE_FRONT = True
-
 #: (H, W, cin) at which the probe front beat today's launch by more than 3 x the run-to-run spread (profiles/probe_front.txt)
 PROBE_FRONT_SHAPES = {(28, 28, 1)}
-
 PROBE_CLASSES = 13
-
-#: evaluation, couplers that take the probe front, two or more residual blocks: h_0 = conv0(mask . v) is never written -- block 0's
-#: conv2, its only reader, forms it from a one-channel seed panel in one extra K-step (False: the thin launch and a residual read)
-SEED_RESIDUAL = True
 
 
 def probe_plan(mask):
@@ -1962,132 +1947,147 @@ def probe_front(conv0, conv1, T, view, plan, factor, ymask, scratch, u, H, W):
                 plan["cls"], u, hid * HW * nc, hid * nc, B, view.cin, H, W, nc, plan["ns"], ymask=ymask)
 
 
+class TangentPlan(NamedTuple):
+    """The launch set of one ResNet coupler's tangent sweep: ``resnet_tangent_plan`` decides, ``_resnet_tangent`` executes.  Anything
+    but the plain form is evaluation only, on the split-precision kernel, for a network of whole 64-channel groups."""
+    #: a block's conv1 gets c1's bit mask as its store filter.  A split-precision launch that takes relu' from a BitMask does not fetch
+    #: the (channel, pixel) rows of its input whose bit is clear, and ``u``, the output of a block's conv1, has exactly one reader -- that
+    #: block's conv2 in whichever form, through relu'(c1) -- so conv1 leaves those rows unwritten (they hold whatever the buffer held).
+    #: The invariant: *a tensor with unwritten rows is only ever read by a launch that does not fetch those rows*.  Training keeps
+    #: full stores: ``net_cotangent`` and the weight gradients read the saved ``u``.
+    filt: bool
+    #: how block 0 gets h_0 and u_0.  "plain": the thin conv0 launch, then conv1 on every column.  "probe": conv1 on one probe column per
+    #: input class (13 per input channel) and the apply kernel form u_0 (csrc/probe_front.hip); h_0 is still the thin launch's.  "seeded":
+    #: the probe front, and h_0 is never written -- block 0's conv2, its only reader, forms it from a one-channel seed panel.
+    front: str
+    #: how the last block reaches the network's output.  "plain": conv1, conv2, the 1x1 conv.  "live": a checkerboard layer reads (s, t,
+    #: s-dot, t-dot) at its (1 - mask) pixels alone (acl.py:48-66) and the 1x1 conv is pointwise, so conv2 (with its residual read) and the
+    #: 1x1 conv (on a gathered last activation) run on those pixels only.  "head": conv2 and the 1x1 conv as ONE fp32 launch that never
+    #: forms h_K (csrc/conv_head.hip).  "block": that launch takes in conv1 too -- no conv1 launch, no ``u`` (csrc/conv_block_head.hip).
+    tail: str
+    #: the returned stack holds the live pixels only, (B, cout * HW/2, nc), pixel (row, col) at row * W/2 + col // 2 (``Tangent.compact``).
+    #: Always under "live"; under "head" / "block" it follows CHECKERBOARD_TAIL alone, the same arithmetic per pixel either way (that
+    #: switch stays bit-neutral: the full form is no speed claim).
+    compact: bool
+
+
+def resnet_tangent_plan(net, view, nc, layout, acts, training):
+    """The TangentPlan of a ResNet coupler ``net`` read through ``view`` for a sweep of ``nc`` column slots in ``layout`` over the
+    primal activations ``acts``; ``training``: the sweep saves its tangents.  Host logic on shapes, types and the module switches (read
+    on every call) only: no device, no launch, no allocation."""
+    conv0, blocks, convf = _resnet_parts(net)
+    hid, cout, nb, H, W = conv0.out_channels, convf.out_channels, len(blocks), view.geom.H, view.geom.W
+    # every form below belongs to the split kernel (whose shapes have an even W) and to evaluation: training keeps every tensor
+    if training or hid % 64 or not _use_bf16x3(9, hid, W, False, H, hid):
+        return TangentPlan(False, "plain", "plain", False)
+    filt = bool(SKIP_DEAD_ROWS)
+    # the other forms replace launches of a block and read the activations in the standard layout
+    if nb == 0 or getattr(acts, "f_group", 1) != 1:
+        return TangentPlan(filt, "plain", "plain", False)
+    bits, live = (lambda i: isinstance(acts[i], BitMask)), view.live is not None
+    # folded head, checkerboard couplers only: on every pixel of a 14 x 14 image the folded launch did not beat the two launches by
+    # more than their own run-to-run spread (profiles/fold_head.txt), so the split-channel couplers keep them
+    head = FOLD_HEAD and live and hid == 64 and cout <= 8 and nc % 16 == 0 and bits(2 * nb - 1)
+    # folded block: block 0 belongs to the probe front and the seeded residual, hence two blocks or more
+    block = head and FOLD_BLOCK and nb >= 2 and bits(2 * nb - 2) and (H, W, cout) in FOLD_BLOCK_SHAPES
+    tail = "block" if block else "head" if head else "live" if CHECKERBOARD_TAIL and live else "plain"
+    front, probe = "plain", view.probe
+    if (PROBE_FRONT and probe is not None and hid == 64 and view.mask is not None and layout == "panel" and nc % 16 == 0
+            and nc > 16 * probe["ns"] and (H, W, view.cin) in PROBE_FRONT_SHAPES):
+        # seeded residual: under the probe front h_0 has ONE reader, block 0's conv2.  With one block that reader is the folded head,
+        # which takes h as a tensor: that coupler keeps the thin launch
+        front = "seeded" if SEED_RESIDUAL and view.cin == 1 and nb >= 2 and bits(1) else "probe"
+    return TangentPlan(filt, front, tail, bool(CHECKERBOARD_TAIL and live))
+
+
 def net_tangent(net, T, view, acts, transpose_packs=False, save=None):
-    """Push all Jacobian columns of ``T`` through the coupler network; returns the raw tangent of the
-    network's pre-activation output (the ScaledTanh derivative ``g`` is applied by acl_tangent).
-    ``save`` (a list, training): the input tangent of every conv / linear layer is kept and appended, in forward order
-    (the network's own input as a compact copy of the rows it reads), for ``net_cotangent(..., saved=, grads=)``.
-    Checkerboard couplers (``view.live``, evaluation only): a checkerboard layer reads (s, t, s-dot, t-dot) at its (1 - mask)
-    pixels alone (acl.py:48-66) and the network's last layer is a pointwise 1x1 conv, so the LAST hidden conv (with its residual
-    read) and the 1x1 conv run on those pixels only; the returned stack is then COMPACT -- (B, cout * HW/2, nc), pixel (row, col)
-    at row * W/2 + col // 2 -- and carries ``compact = True`` (``AffineCouplingBijection.decode_`` switches index maps).
-    Dead rows (``SKIP_DEAD_ROWS``, evaluation only): a split-precision launch that takes relu' from a BitMask does not fetch the
-    (channel, pixel) rows of its input whose bit is clear.  ``u``, the output of a block's conv1, has exactly one reader here -- that
-    block's conv2, through relu'(c1) -- so when that reader is such a launch, conv1 gets c1's mask as its store filter and leaves
-    those rows unwritten (they hold whatever the buffer held).  The invariant: *a tensor with unwritten rows is only ever read by a
-    launch that does not fetch those rows*.  Training (``save``) keeps full stores: ``net_cotangent`` and the weight gradients read
-    the saved ``u``.
-    Folded block (``FOLD_BLOCK``, shapes in ``FOLD_BLOCK_SHAPES``): where the folded head runs and the network has two or more
-    blocks, the last block issues no conv1 launch and no ``u``: one launch takes ``h_{K-1}`` to the network's output."""
-    geo, B, nc, dev = view.geom, T.B, T.nc, T.data.device
+    """Push all Jacobian columns of ``T`` through the coupler network; returns the raw tangent of the network's pre-activation output
+    (the ScaledTanh derivative ``g`` is applied by acl_tangent).  ``save`` (a list, training): the input tangent of every conv / linear
+    layer is kept and appended, in forward order (the network's own input as a compact copy of the rows it reads), for
+    ``net_cotangent(..., saved=, grads=)``.  Which launches a ResNet coupler gets, and what they may leave unwritten: ``TangentPlan``."""
     if save is not None:
         save.append(_view_rows(T, view))
-    if net.kind == "resnet":
-        conv0, blocks, convf = _resnet_parts(net)
-        hid, cout, H, W, HW = conv0.out_channels, convf.out_channels, geo.H, geo.W, geo.HW
-        new = lambda c: Tangent(B, c * HW, nc, "panel", dev)
-        pn = lambda c: (c * HW * nc, HW * nc, nc)          # (np, chan, px) strides of a panel with c channels
-        # Hidden tangents live SLICE-MAJOR, [sample][pixel][16-column slice][channel][16]: the 16 channels x 16 columns an
-        # MFMA wave stores (or reads as residual) per instruction are then one contiguous KiB instead of sixteen 64-byte
-        # pieces in sixteen channel planes -- that access shape ran at 13 B/clk/CU against 48 (tools/ubench/curate2.py)
-        # and was the 15k-cycle tail of every work item.  Only the kernels' strides know about it.
-        hd = (hid * HW * nc, 16, hid * nc)                   # (np, chan, px)
-        hsl = hid * 16                                       # slice stride
-        fg = getattr(acts, "f_group", 1)                     # primal activations: (B,C,H,W) or (B/16,C,H,W,16)
-        fs = dict(f_np=hid * HW * fg, f_ci=HW * fg, f_px=fg, f_group=fg)
-        # relu' source of a hidden conv: float activations, or the bit mask the primal pass wrote (BitMask)
-        fk = lambda t: dict(fmode=F_RELU_BITS, f=t.data, f_np=t.np_bytes) if isinstance(t, BitMask) else dict(fmode=F_RELU, f=t, **fs)
-        u, h2 = new(hid), new(hid)
-        compact = (CHECKERBOARD_TAIL and view.live is not None and save is None and fg == 1 and len(blocks) > 0 and hid % 64 == 0
-                   and W % 2 == 0 and _use_bf16x3(9, hid, W, False, H, hid))
-        # conv2 of every block (full or checkerboard form) reads u on the split kernel with c1's bit mask: see the docstring
-        filt = SKIP_DEAD_ROWS and save is None and hid % 64 == 0 and _use_bf16x3(9, hid, W, False, H, hid)
-        # folded head: the last block's conv2 and the 1x1 conv as one launch that never forms h_K (csrc/conv_head.hip).  Checkerboard
-        # couplers only: on every pixel of a 14 x 14 image the folded launch did not beat the two launches by more than their own
-        # run-to-run spread (profiles/fold_head.txt), so the split-channel couplers keep them.  (The full-image form these couplers
-        # take under CHECKERBOARD_TAIL = False exists to keep that off-switch bit-neutral: it is not a speed claim.)
-        fold = (FOLD_HEAD and view.live is not None and save is None and fg == 1 and len(blocks) > 0 and hid == 64 and cout <= 8 and nc % 16 == 0
-                and isinstance(acts[2 * len(blocks) - 1], BitMask) and _use_bf16x3(9, hid, W, False, H, hid))
-        # folded block: the last block's conv1 goes into the folded launch as well (csrc/conv_block_head.hip); block 0 belongs to the
-        # probe front and the seeded residual
-        nb = len(blocks)
-        fold_block = (FOLD_BLOCK and fold and nb >= 2 and isinstance(acts[2 * nb - 2], BitMask) and isinstance(acts[2 * nb - 1], BitMask)
-                      and (H, W, cout) in FOLD_BLOCK_SHAPES)
-        # probe front (csrc/probe_front.hip): block 0's conv1 on the plan's probe columns instead of all nc, then the apply kernel.
-        # Only u_0 changes producer: h_0 on every column is still the thin kernel's (block 0's conv2 reads it as its residual).
-        plan = getattr(view, "probe", None)
-        probe = (PROBE_FRONT and plan is not None and save is None and fg == 1 and len(blocks) > 0 and hid == 64 and view.mask is not None
-                 and T.layout == "panel" and nc % 16 == 0 and nc > 16 * plan["ns"] and (H, W, view.cin) in PROBE_FRONT_SHAPES
-                 and cfg().tangent == "bf16x3" and _use_bf16x3(9, hid, W, False, H, hid))
-        # seeded residual: under the probe front h_0 has ONE reader, block 0's conv2 (as its residual), which can form it from mask . v
-        # itself -- the thin launch and h_0 go.  With one block the folded head reads h as its residual: that coupler keeps them.
-        seeded = SEED_RESIDUAL and probe and view.cin == 1 and len(blocks) >= 2 and isinstance(acts[1], BitMask)
-        h = None
-        if not seeded:
-            h = new(hid)
-            conv_tangent(T.data, view.chan_off * HW * nc, T.t_b, view.chan_step * HW * nc, nc, conv0.weight, 9, h.data, *hd,
-                         B, view.cin, hid, H, W, nc, fmode=F_RAW if view.mask is not None else F_NONE, f=view.mask, f_np=0,
-                         f_ci=HW, f_px=1, y_sl=hsl)
-        for k, blk in enumerate(blocks):
-            a_in, c1 = acts[2 * k], acts[2 * k + 1]
-            ym = c1 if filt and isinstance(c1, BitMask) else None
-            if fold_block and k + 1 == nb:
-                # no conv1 launch, no u: one launch from h_{K-1} to yt (compact or full, the same arithmetic per pixel)
-                HWo = HW // 2 if compact else HW
-                yt = Tangent(B, cout * HWo, nc, "panel", dev)
-                conv_tangent(h.data, 0, *hd, blk.conv2.weight, 9, yt.data, cout * HWo * nc, HWo * nc, nc, B, hid, hid, H, W, nc,
-                             x_sl=hsl, live=view.live["parity"] if compact else 0,
-                             head=dict(weight=convf.weight, act=acts[-1], conv1=dict(weight=blk.conv1.weight, mask=c1)), **fk(a_in))
-                if compact:
-                    yt.compact = True
-                return yt
-            if probe and k == 0:
-                # the responses go through h2's buffer: free until conv2 writes it, after the apply kernel has read them
-                probe_front(conv0, blk.conv1, T, view, plan, fk(a_in), ym, h2.data, u.data, H, W)
-            else:
-                conv_tangent(h.data, 0, *hd, blk.conv1.weight, 9, u.data, *hd, B, hid, hid, H, W, nc, x_sl=hsl, y_sl=hsl, **fk(a_in),
-                             ymask=ym)
-            if seeded and k == 0:
-                sd = seed_panel(T, view, H, W)
-                conv_tangent(u.data, 0, *hd, blk.conv2.weight, 9, h2.data, *hd, B, hid, hid, H, W, nc, x_sl=hsl, y_sl=hsl,
-                             seed=dict(sd, pack=_seed_pack(conv0, dev)), **fk(c1))
-                h, h2 = h2, new(hid)
-                continue
-            if fold and k + 1 == len(blocks):
-                # compact (checkerboard) or full output, the same arithmetic per pixel: CHECKERBOARD_TAIL stays bit-neutral
-                HWo = HW // 2 if compact else HW
-                yt = Tangent(B, cout * HWo, nc, "panel", dev)
-                conv_tangent(u.data, 0, *hd, blk.conv2.weight, 9, yt.data, cout * HWo * nc, HWo * nc, nc, B, hid, hid, H, W, nc,
-                             res_t=h.data, res_np=hd[0], x_sl=hsl, live=view.live["parity"] if compact else 0,
-                             head=dict(weight=convf.weight, act=acts[-1]), **fk(c1))
-                if compact:
-                    yt.compact = True
-                return yt
-            if compact and k + 1 == len(blocks):
-                # the last hidden conv at the live pixels only, stored compactly; its residual read at those pixels of the full h
-                HWc = HW // 2
-                hc = Tangent(B, hid * HWc, nc, "panel", dev)
-                conv_tangent(u.data, 0, *hd, blk.conv2.weight, 9, hc.data, hid * HWc * nc, 16, hid * nc, B, hid, hid, H, W, nc,
-                             res_t=h.data, res_np=hd[0], x_sl=hsl, y_sl=hsl, live=view.live["parity"], **fk(c1))
-                a_last = gather_primal(acts[-1], view.live["act_idx"], hid * HWc)         # relu' source of the 1x1 conv, compact too
-                yt = Tangent(B, cout * HWc, nc, "panel", dev)
-                conv_tangent(hc.data, 0, hid * HWc * nc, 16, hid * nc, convf.weight, 1, yt.data, cout * HWc * nc, HWc * nc, nc, B, hid,
-                             cout, H, W // 2, nc, fmode=F_RELU, f=a_last, x_sl=hsl, f_np=hid * HWc, f_ci=HWc, f_px=1)
-                yt.compact = True
-                return yt
-            conv_tangent(u.data, 0, *hd, blk.conv2.weight, 9, h2.data, *hd, B, hid, hid, H, W, nc, res_t=h.data, x_sl=hsl,
-                         y_sl=hsl, **fk(c1))
-            if save is not None:                              # keep h_k and u_k: no ping-pong reuse
-                save += [h, u]
-                h, u, h2 = h2, new(hid), new(hid)
-            else:
-                h, h2 = h2, h
-        if save is not None:
-            save.append(h)
-        yt = new(cout)
-        conv_tangent(h.data, 0, *hd, convf.weight, 1, yt.data, *pn(cout), B, hid, cout, H, W, nc, fmode=F_RELU,
-                     f=acts[-1], x_sl=hsl, **fs)
+    return (_resnet_tangent if net.kind == "resnet" else _mlp_tangent)(net, T, view, acts, save)
+
+
+def _resnet_tangent(net, T, view, acts, save):
+    """``net_tangent`` of a ResNet coupler: the launches its TangentPlan names, in forward order."""
+    geo, B, nc, dev = view.geom, T.B, T.nc, T.data.device
+    conv0, blocks, convf = _resnet_parts(net)
+    hid, cout, H, W, HW, nb = conv0.out_channels, convf.out_channels, geo.H, geo.W, geo.HW, len(blocks)
+    plan = resnet_tangent_plan(net, view, nc, T.layout, acts, save is not None)
+    new = lambda c: Tangent(B, c * HW, nc, "panel", dev)
+    # Hidden tangents live SLICE-MAJOR, [sample][pixel][16-column slice][channel][16]: the 16 channels x 16 columns an MFMA wave stores
+    # (or reads as residual) per instruction are then one contiguous KiB instead of sixteen 64-byte pieces in sixteen channel planes --
+    # that access shape ran at 13 B/clk/CU against 48 (tools/ubench/curate2.py) and was the 15k-cycle tail of every work item.  Only
+    # the kernels' strides know about it.
+    hd, hsl = (hid * HW * nc, 16, hid * nc), hid * 16    # (np, chan, px) strides, slice stride
+    fg = getattr(acts, "f_group", 1)                     # primal activations: (B,C,H,W) or (B/16,C,H,W,16)
+    fs = dict(f_np=hid * HW * fg, f_ci=HW * fg, f_px=fg, f_group=fg)
+    # relu' source of a hidden conv: float activations, or the bit mask the primal pass wrote (BitMask)
+    fk = lambda t: dict(fmode=F_RELU_BITS, f=t.data, f_np=t.np_bytes) if isinstance(t, BitMask) else dict(fmode=F_RELU, f=t, **fs)
+
+    def folded(x, blk, factor, **kw):
+        """The last block's conv2 and the 1x1 conv as one launch from ``x`` to the network's output, compact or full."""
+        HWo = HW // 2 if plan.compact else HW
+        yt = Tangent(B, cout * HWo, nc, "panel", dev, compact=plan.compact)
+        conv_tangent(x.data, 0, *hd, blk.conv2.weight, 9, yt.data, cout * HWo * nc, HWo * nc, nc, B, hid, hid, H, W, nc, x_sl=hsl,
+                     live=view.live["parity"] if plan.compact else 0, **kw, **factor)
         return yt
+
+    u, h2, h = new(hid), new(hid), None
+    if plan.front != "seeded":
+        h = new(hid)
+        conv_tangent(T.data, view.chan_off * HW * nc, T.t_b, view.chan_step * HW * nc, nc, conv0.weight, 9, h.data, *hd,
+                     B, view.cin, hid, H, W, nc, fmode=F_RAW if view.mask is not None else F_NONE, f=view.mask, f_np=0,
+                     f_ci=HW, f_px=1, y_sl=hsl)
+    for k, blk in enumerate(blocks):
+        a_in, c1, last = acts[2 * k], acts[2 * k + 1], k + 1 == nb
+        ym = c1 if plan.filt and isinstance(c1, BitMask) else None
+        if last and plan.tail == "block":
+            return folded(h, blk, fk(a_in), head=dict(weight=convf.weight, act=acts[-1], conv1=dict(weight=blk.conv1.weight, mask=c1)))
+        if k == 0 and plan.front != "plain":
+            # the responses go through h2's buffer: free until conv2 writes it, after the apply kernel has read them
+            probe_front(conv0, blk.conv1, T, view, view.probe, fk(a_in), ym, h2.data, u.data, H, W)
+        else:
+            conv_tangent(h.data, 0, *hd, blk.conv1.weight, 9, u.data, *hd, B, hid, hid, H, W, nc, x_sl=hsl, y_sl=hsl, **fk(a_in),
+                         ymask=ym)
+        if k == 0 and plan.front == "seeded":
+            sd = seed_panel(T, view, H, W)
+            conv_tangent(u.data, 0, *hd, blk.conv2.weight, 9, h2.data, *hd, B, hid, hid, H, W, nc, x_sl=hsl, y_sl=hsl,
+                         seed=dict(sd, pack=_seed_pack(conv0, dev)), **fk(c1))
+            h, h2 = h2, new(hid)
+            continue
+        if last and plan.tail == "head":
+            return folded(u, blk, fk(c1), res_t=h.data, res_np=hd[0], head=dict(weight=convf.weight, act=acts[-1]))
+        if last and plan.tail == "live":
+            # the last hidden conv at the live pixels only, stored compactly; its residual read at those pixels of the full h
+            HWc = HW // 2
+            hc = Tangent(B, hid * HWc, nc, "panel", dev)
+            conv_tangent(u.data, 0, *hd, blk.conv2.weight, 9, hc.data, hid * HWc * nc, 16, hid * nc, B, hid, hid, H, W, nc,
+                         res_t=h.data, res_np=hd[0], x_sl=hsl, y_sl=hsl, live=view.live["parity"], **fk(c1))
+            a_last = gather_primal(acts[-1], view.live["act_idx"], hid * HWc)         # relu' source of the 1x1 conv, compact too
+            yt = Tangent(B, cout * HWc, nc, "panel", dev, compact=True)
+            conv_tangent(hc.data, 0, hid * HWc * nc, 16, hid * nc, convf.weight, 1, yt.data, cout * HWc * nc, HWc * nc, nc, B, hid,
+                         cout, H, W // 2, nc, fmode=F_RELU, f=a_last, x_sl=hsl, f_np=hid * HWc, f_ci=HWc, f_px=1)
+            return yt
+        conv_tangent(u.data, 0, *hd, blk.conv2.weight, 9, h2.data, *hd, B, hid, hid, H, W, nc, res_t=h.data, x_sl=hsl,
+                     y_sl=hsl, **fk(c1))
+        if save is not None:                              # keep h_k and u_k: no ping-pong reuse
+            save += [h, u]
+            h, u, h2 = h2, new(hid), new(hid)
+        else:
+            h, h2 = h2, h
+    if save is not None:
+        save.append(h)
+    yt = new(cout)
+    conv_tangent(h.data, 0, *hd, convf.weight, 1, yt.data, cout * HW * nc, HW * nc, nc, B, hid, cout, H, W, nc, fmode=F_RELU,
+                 f=acts[-1], x_sl=hsl, **fs)
+    return yt
+
+
+def _mlp_tangent(net, T, view, acts, save):
+    B, nc, dev = T.B, T.nc, T.data.device
     lins = [m for m in net if isinstance(m, nn.Linear)]
     x_t, x_off, x_ci, cin = T.data, view.chan_off * B * nc, view.chan_step * B * nc, view.cin
     fmode, f, f_px = F_NONE, None, 0
