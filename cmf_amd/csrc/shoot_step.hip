@@ -1,0 +1,178 @@
+// The per-sample float64 step of geodesic shooting: between the Gram matrix of a d-column decode sweep and the narrow
+// sweep over the velocity.
+//
+// cmf_metric_solve takes G = J^T J as one cmf_gram_cholesky attempt leaves it (float32, the lower triangle is read) and a float64
+// right-hand side per sample, and computes in float64
+//   solve:  out = G^-1 rhs   (the velocity v of the momentum p: z' = G^-1 p),
+//   apply:  out = G rhs      (the momentum p of the initial velocity v), the symmetric product from the lower triangle,
+//   stats = { rhs^T out, max_k |out_k| }   (solve: rhs^T out = p^T v, the squared speed).
+// One 256-thread workgroup per sample; nothing is shared between workgroups, there are no atomics.
+//
+//   1. The lower triangle of G is loaded into the float64 matrix A in LDS, with rhs as row d below it.  The row stride is d | 1:
+//      odd, so that the column reads of the elimination (16 rows of one column per wave) spread over the banks.
+//   2. solve: Cholesky without square roots on the lower triangle -- the elimination of gn_step.hip / gram_cond.hip, restated here
+//      so that those kernels keep their bits: A_ij -= A_ik A_jk / p_k for k < j <= i, one barrier per column; the pivots p_k land
+//      on the diagonal.  Row d takes part like any other row, which IS the forward substitution.  Then the back substitution on row
+//      d, last column first, one barrier per column.
+//      apply: thread i sums A_[max(i,j)][min(i,j)] rhs_j over j = 0 .. d - 1 in that order.
+//   3. rhs^T out and max |out_k|: one value per thread, folded by a fixed binary tree in LDS.
+// The order of every sum is a function of d alone.
+//
+// info: 0 ok; 1 (solve) a pivot that is not positive and finite (out64, out32, stats = NaN); 2 a non-finite value in the lower
+// triangle of jtj or in rhs (every output NaN).
+#include "common.h"
+
+namespace {
+
+constexpr int NT = 256;
+constexpr int MAXD = 128;
+constexpr int SMALL = NT + MAXD;                  // doubles: the tree's partials [NT], out [MAXD]; then A [(d + 1) * row_stride(d)]
+
+inline __host__ __device__ int row_stride(int d) { return d | 1; }
+
+__device__ __forceinline__ bool not_finite(float v) { return !(fabsf(v) <= __FLT_MAX__); }
+__device__ __forceinline__ bool not_finite(double v) { return !(fabs(v) <= __DBL_MAX__); }
+
+// Fold one value per thread by a fixed binary tree (sum, or maximum with MAX); the result in every thread.  part: NT doubles
+// that nobody else touches between the two barriers that bracket the call.
+template <bool MAX>
+__device__ __forceinline__ double block_fold(double v, double* part) {
+  const int tid = threadIdx.x;
+  part[tid] = v;
+  __syncthreads();
+  for (int s = NT / 2; s > 0; s >>= 1) {
+    if (tid < s) {
+      const double a = part[tid], c = part[tid + s];
+      part[tid] = MAX ? (c > a ? c : a) : a + c;
+    }
+    __syncthreads();
+  }
+  const double out = part[0];
+  __syncthreads();                                // part may be rewritten by the caller
+  return out;
+}
+
+template <bool APPLY>
+__global__ __launch_bounds__(NT) void metric_solve_kernel(const float* __restrict__ jtj, const double* __restrict__ rhs, int d,
+                                                           double* __restrict__ out64, float* __restrict__ out32,
+                                                           double* __restrict__ stats, int* __restrict__ info) {
+  extern __shared__ __attribute__((aligned(16))) double lds[];
+  const int tid = threadIdx.x, b = blockIdx.x;
+  double* part = lds;
+  double* xs = lds + NT;                          // [MAXD]
+  double* A = lds + SMALL;                        // [(d + 1) * LD]
+  const int LD = row_stride(d), dd = d * d;
+  const double nan = __builtin_nan("");
+  const long long ob = (long long)b * d;
+
+  // 1. the lower triangle of G, rhs below it
+  int bad = 0;
+  const float* __restrict__ G = jtj + (long long)b * dd;
+  for (int e = tid; e < dd; e += NT) {
+    const int i = e / d, j = e - i * d;
+    if (j <= i) {
+      const float v = G[e];
+      bad |= not_finite(v);
+      A[i * LD + j] = (double)v;
+    }
+  }
+  double rk = 0.0;                                // thread k < d keeps rhs_k
+  if (tid < d) {
+    rk = rhs[ob + tid];
+    bad |= not_finite(rk);
+    A[d * LD + tid] = rk;
+  }
+  if (__syncthreads_or(bad)) {                    // uniform; the barrier also publishes A
+    if (tid < d) {
+      out64[ob + tid] = nan;
+      out32[ob + tid] = (float)nan;
+    }
+    if (tid < 2) stats[2LL * b + tid] = nan;
+    if (tid == 0) info[b] = 2;
+    return;
+  }
+
+  double ok = 0.0;                                // thread k < d: out_k
+  if (APPLY) {
+    // 2. out_i = sum_j G_ij rhs_j, j ascending
+    if (tid < d) {
+      const double* r = A + d * LD;
+      for (int j = 0; j < d; ++j) ok += (j <= tid ? A[tid * LD + j] : A[j * LD + tid]) * r[j];
+    }
+  } else {
+    // 2. pivots and multipliers; row d is rhs
+    const int ti = tid >> 4, tj = tid & 15;
+    int fail = 0;
+    for (int k = 0; k < d; ++k) {
+      const double piv = A[k * LD + k];           // uniform
+      if (!(piv > 0.0) || !(piv < 1.0e300)) {
+        fail = 1;
+        break;
+      }
+      for (int i = k + 1 + ti; i <= d; i += 16) {
+        const double aik = A[i * LD + k] / piv;    // a division: x / x = 1, a duplicate column cancels its pivot exactly
+        const int jmax = i < d ? i : d - 1;
+        for (int j = k + 1 + tj; j <= jmax; j += 16) A[i * LD + j] -= aik * A[j * LD + k];
+      }
+      __syncthreads();
+    }
+    if (fail) {                                   // uniform
+      if (tid < d) {
+        out64[ob + tid] = nan;
+        out32[ob + tid] = (float)nan;
+      }
+      if (tid < 2) stats[2LL * b + tid] = nan;
+      if (tid == 0) info[b] = 1;
+      return;
+    }
+    // the back substitution on row d
+    double* w = A + d * LD;
+    for (int i = d - 1; i >= 0; --i) {
+      const double di = w[i] / A[i * LD + i];
+      if (tid < i) w[tid] -= A[i * LD + tid] * di;
+      if (tid == i) xs[i] = di;
+      __syncthreads();
+    }
+    if (tid < d) ok = xs[tid];
+  }
+
+  // 3. the outputs and the two statistics
+  if (tid < d) {
+    out64[ob + tid] = ok;
+    out32[ob + tid] = (float)ok;
+  }
+  const double dot = block_fold<false>(tid < d ? rk * ok : 0.0, part);
+  const double big = block_fold<true>(tid < d ? fabs(ok) : 0.0, part);
+  if (tid == 0) {
+    stats[2LL * b] = dot;
+    stats[2LL * b + 1] = big;
+    info[b] = 0;
+  }
+}
+
+template <bool APPLY>
+int launch(const float* jtj, const double* rhs, int d, int B, double* out64, float* out32, double* stats, int* info,
+           hipStream_t s) {
+  const size_t lds = sizeof(double) * ((size_t)SMALL + (size_t)(d + 1) * row_stride(d));
+  if (lds > 48 * 1024) {
+    hipError_t e = cmf_set_dynamic_lds((const void*)metric_solve_kernel<APPLY>, (int)lds);
+    if (e != hipSuccess) return (int)e;
+  }
+  hipLaunchKernelGGL(metric_solve_kernel<APPLY>, dim3(B), dim3(NT), lds, s, jtj, rhs, d, out64, out32, stats, info);
+  CMF_LAUNCH_CHECK();
+  return 0;
+}
+
+}  // namespace
+
+extern "C" int cmf_metric_solve(const float* jtj, const double* rhs, int d, int B, int apply, double* out64, float* out32,
+                                double* stats, int* info, void* stream) {
+  if (!jtj || !rhs || !out64 || !out32 || !stats || !info || B <= 0) return CMF_EINVAL;
+  if (d < 1 || d > MAXD || (apply != 0 && apply != 1)) return CMF_EINVAL;
+  if ((uintptr_t)jtj % 4 || (uintptr_t)rhs % 8 || (uintptr_t)out64 % 8 || (uintptr_t)out32 % 4 || (uintptr_t)stats % 8 ||
+      (uintptr_t)info % 4)
+    return CMF_EINVAL;
+  hipStream_t s = (hipStream_t)stream;
+  return apply ? launch<true>(jtj, rhs, d, B, out64, out32, stats, info, s)
+               : launch<false>(jtj, rhs, d, B, out64, out32, stats, info, s);
+}

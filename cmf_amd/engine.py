@@ -1200,6 +1200,60 @@ def curve_step(T, jtj, cross, xhat, points, damping):
     return r
 
 
+#: widest metric ``metric_solve`` takes: the float64 matrix of a sample lives in LDS (csrc/shoot_step.hip)
+SHOOT_MAX_WIDTH = 128
+
+
+class MetricSolveResult:
+    """Outputs of ``metric_solve`` (all on the device): ``out64`` (B, d) float64 = G^-1 rhs (or G rhs), ``out32`` (B, d) float32,
+    the same values rounded, ``stats`` (B, 2) float64 = [rhs^T out, max |out_k|], ``info`` (B,) int32 (0 ok, 1 non-positive pivot:
+    out and stats NaN, 2 non-finite input: everything NaN)."""
+    __slots__ = ("out64", "out32", "stats", "info")
+
+
+def metric_solve(jtj, rhs, apply=False):
+    """The per-sample float64 step of geodesic shooting: from the Gram matrix ``jtj`` (B, d, d) float32 (one
+    ``gram_cholesky`` attempt; the lower triangles are read) and ``rhs`` (B, d) float64, out = G^-1 rhs -- the velocity of a
+    momentum, ``stats[:, 0]`` the squared speed -- or, with ``apply``, out = G rhs -- the momentum of a velocity.  Returns a
+    ``MetricSolveResult``; ``out32[:, :, None]`` is the ``eps`` of a one-direction sweep.  Deterministic per sample; one launch,
+    no synchronisation."""
+    if not isinstance(jtj, torch.Tensor) or not jtj.is_cuda:
+        raise ValueError(f"jtj must be on the GPU, got {getattr(jtj, 'device', type(jtj).__name__)} (there is no CPU fallback)")
+    if jtj.dtype != torch.float32:
+        raise ValueError(f"jtj must be float32, got {jtj.dtype}")
+    if jtj.dim() != 3 or jtj.shape[1] != jtj.shape[2] or not jtj.is_contiguous():
+        raise ValueError(f"jtj must be a contiguous (B, d, d) tensor, got {tuple(jtj.shape)}"
+                         f"{'' if jtj.is_contiguous() else ' (not contiguous)'}")
+    B, d, dev = jtj.shape[0], jtj.shape[1], jtj.device
+    if not 1 <= d <= SHOOT_MAX_WIDTH:
+        raise ValueError(f"d = {d}: the metric solve kernel supports 1 <= d <= {SHOOT_MAX_WIDTH}")
+    if not isinstance(rhs, torch.Tensor) or not rhs.is_cuda:
+        raise ValueError(f"rhs must be on the GPU, got {getattr(rhs, 'device', type(rhs).__name__)} (there is no CPU fallback)")
+    if rhs.dtype != torch.float64:
+        raise ValueError(f"rhs must be float64, got {rhs.dtype}")
+    if rhs.shape != (B, d) or rhs.device != dev or not rhs.is_contiguous():
+        raise ValueError(f"rhs must be a contiguous ({B}, {d}) tensor on {dev}, got {tuple(rhs.shape)} on {rhs.device}"
+                         f"{'' if rhs.is_contiguous() else ' (not contiguous)'}")
+    r = MetricSolveResult()
+    r.out64 = torch.empty(B, d, dtype=torch.float64, device=dev)
+    r.out32 = torch.empty(B, d, dtype=torch.float32, device=dev)
+    r.stats = torch.empty(B, 2, dtype=torch.float64, device=dev)
+    r.info = torch.empty(B, dtype=torch.int32, device=dev)
+    if B == 0:
+        return r
+    launch = lambda: _lib.check(_lib.load().cmf_metric_solve(_p(jtj), _p(rhs), d, B, int(bool(apply)), _p(r.out64), _p(r.out32),
+                                                             _p(r.stats), _p(r.info), _stream()), "cmf_metric_solve")
+    TIMER = _timer()
+    if TIMER is None:
+        launch()
+    else:
+        # float64: the elimination d^3 / 3 with the two substitutions 2 d^2 (apply: the product 2 d^2), the form 2 d; bytes: the
+        # triangle of G and rhs in, the outputs
+        TIMER.wrap("metric_solve", B * ((2.0 * d * d if apply else d ** 3 / 3.0 + 2.0 * d * d) + 2.0 * d),
+                   B * (2.0 * d * (d + 1) + 20.0 * d + 20.0), launch)
+    return r
+
+
 def gram_backward(T, jtj, g_logdet=None, g_l1off=None, g_l1diag=None):
     """Cotangent of the Jacobian stack T for a loss with d/d logdet = g_logdet, d/d l1_off = g_l1off, d/d l1_diag =
     g_l1diag (each (B,) or None): what autograd yields through non_square.py:307-308, :280-294, :87-100."""

@@ -9,7 +9,18 @@ tridiagonal normal equations); nothing leaves the device.
     out = geo.connect(x0.cuda(), x1.cuda())
     out["length"], out["initial_length"]                 # in the head's input space, after and on the straight latent line
     out["path"]                                          # (B, points, *x_shape) in data space
+
+``connect`` is the logarithm side; ``shoot`` is the exponential map: from a point and a latent velocity it walks along
+the manifold's own geodesic by classical RK4 on Hamilton's equations z' = G^-1 p, p' = grad_z 1/2 ||J(z) v||^2 (v held fixed), so no
+second derivative of the decoder is formed.  One evaluation is a primal decode that keeps state, a d-column sweep for G, the
+per-sample float64 solve (csrc/shoot_step.hip), a one-direction sweep that is kept, and the training backward.
+
+    lg = geo.log(x0, x1)                                 # connect + the initial velocity of the relaxed curve
+    out = geo.shoot(x0, lg["velocity"])                  # out["path"][:, -1] is close to x1
+    out = geo.shoot_latents(z0, v0, steps=8, time=0.5)
 """
+import math
+
 import torch
 
 from . import engine as E
@@ -25,9 +36,15 @@ class ManifoldGeodesic:
     A curve has ``points`` >= 3 latents; its ends stay where they are.  ``steps`` iterations per call; every curve carries its own
     damping lambda, started at ``damping``: a step is accepted iff its solve succeeded and it strictly lowers the energy, then
     lambda <- max(lambda ``down``, 1e-12); otherwise the curve stays where it is and lambda <- min(lambda ``up``, 1e8).  The energy is
-    therefore monotone non-increasing, and ``steps=0`` gives the diagnostics of the straight latent line."""
+    therefore monotone non-increasing, and ``steps=0`` gives the diagnostics of the straight latent line.
 
-    def __init__(self, density, points=17, steps=10, damping=1e-3, up=10.0, down=0.1):
+    ``shoot`` / ``shoot_latents`` integrate the geodesic that leaves a point with a given latent velocity in ``shoot_steps`` >= 1
+    RK4 steps (``log`` / ``log_latents``: ``connect`` plus the velocity that takes ``shoot`` from the first end to the second)."""
+
+    def __init__(self, density, points=17, steps=10, damping=1e-3, up=10.0, down=0.1, shoot_steps=16):
+        if int(shoot_steps) < 1:
+            raise ValueError(f"need shoot_steps >= 1, got {shoot_steps}")
+        self.shoot_steps = int(shoot_steps)
         self.density, self.head = density, metric_head(density, "latent", "manifold geodesics")
         d = self.head.program.d
         if d > E.GEODESIC_MAX_WIDTH:
@@ -133,3 +150,150 @@ class ManifoldGeodesic:
         return {"latents": z, "path_head": curves(x_hat), "path": curves(x_data), "energy": energy, "initial_energy": energy_0,
                 "length": lengths.sum(1), "initial_length": lengths_0.sum(1), "segment_lengths": lengths, "gradient": r.grad,
                 "gradient_max": r.stats[:, 3].contiguous(), "accepted": accepted, "damping": lam, "info": r.info}
+
+    # -- the exponential map -----------------------------------------------------------------
+    @torch.no_grad()
+    def log(self, x0, x1, steps=None):
+        """``connect(x0, x1, steps)`` and, beside its values, ``velocity`` (B, d) float64: the latent velocity of the relaxed curve at
+        its start, the second-order one-sided difference N (-3 z_0 + 4 z_1 - z_2) / 2 of its ``latents`` -- what ``shoot`` takes to
+        walk from ``x0`` to ``x1`` in time 1."""
+        return self._with_velocity(self.connect(x0, x1, steps))
+
+    @torch.no_grad()
+    def log_latents(self, z0, z1, steps=None):
+        """``connect_latents(z0, z1, steps)`` with the ``velocity`` of ``log``."""
+        return self._with_velocity(self.connect_latents(z0, z1, steps))
+
+    def _with_velocity(self, out):
+        z = out["latents"].double()
+        out = dict(out)
+        out["velocity"] = (self.points - 1) * (-3.0 * z[:, 0] + 4.0 * z[:, 1] - z[:, 2]) / 2.0
+        return out
+
+    def _metric(self, z32):
+        """One primal decode at ``z32`` that keeps state and the unsaved d-column sweep over it: (x_hat, primal contexts, jtj)."""
+        prog = self.head.program
+        x_hat, _, pctx = prog.decode_train(z32, tangents=False, nc_hint=16)
+        T, _ = prog.decode_tangents_from_ctx(pctx)
+        jtj = E.gram_cholesky(T, prog.d, 1).jtj
+        del T
+        return x_hat, pctx, jtj
+
+    @torch.no_grad()
+    def shoot_evaluate(self, z, p, grads, backward=True, metric=None):
+        """The right-hand side of Hamilton's equations at the latents ``z`` (B, d) float32 and momenta ``p`` (B, d) float64:
+        returns (p' (B, d) float64, v = G^-1 p (B, d) float64, p^T v (B,) float64, info (B,) int32, x_hat).  ``info``: the code of
+        ``engine.metric_solve`` (0 ok; 1 a non-positive pivot of G, 2 a non-finite value: v, p' and the speed are NaN).  ``grads``: an
+        ``engine.GradPool`` over the head's parameters that the backward fills and nobody reads.  ``backward=False``
+        stops after the solve (p' is None); ``metric``: the result of ``_metric(z)`` where the caller has it already."""
+        prog = self.head.program
+        with E.scope(self.head.kernels):
+            x_hat, pctx, jtj = self._metric(z) if metric is None else metric
+            r = E.metric_solve(jtj, p)
+            speed2 = r.stats[:, 0].contiguous()
+            if not backward:
+                return None, r.out64, speed2, r.info, x_hat
+            TV, ctx = prog.decode_tangents_from_ctx(pctx, eps=r.out32[:, :, None], nc=16, save=True)
+            # 1/2 ||J v||^2 of the one direction v: its cotangent on the stack is J v itself, in place in a copy
+            Ct = E.Tangent(TV.B, TV.N, TV.nc, TV.layout, TV.data.device, data=TV.data.clone(), compact=TV.compact)
+            dz = prog.decode_backward(ctx, Ct, torch.zeros_like(x_hat), grads)
+        return dz.double(), r.out64, speed2, r.info, x_hat
+
+    @torch.no_grad()
+    def shoot(self, x, v0, steps=None, time=1.0):
+        """The geodesic that leaves the input ``x`` (the density's input, (B, *x_shape), as for ``connect``; never modified) with the
+        latent velocity ``v0`` (B, d): ``shoot_latents`` from the encoder's latent."""
+        E.require_gpu(x, "x")
+        if x.shape[0] == 0:
+            raise ValueError("shoot needs at least one input")
+        with E.scope(self.head.kernels):
+            z0 = self.projector.head_input_and_latent(x)[1]
+        return self.shoot_latents(z0, v0, steps, time)
+
+    @torch.no_grad()
+    def shoot_latents(self, z0, v0, steps=None, time=1.0):
+        """Walk from the head's latents ``z0`` (B, d) float32 with the latent velocities ``v0`` (B, d) (float64, or float32) for
+        ``time`` along the geodesics of the pull-back metric G = J^T J: classical RK4 with ``steps`` (default ``shoot_steps``) equal
+        steps on z' = G^-1 p, p' = grad_z 1/2 ||J(z) v||^2, from p_0 = G(z_0) v_0.  z and p are carried in float64; the decoder sees
+        ``z.float()``.  Returns device tensors for the B trajectories of S + 1 nodes:
+          ``latents`` (B, S + 1, d) float32; ``velocity`` and ``momentum`` (B, S + 1, d) float64; ``speed2`` (B, S + 1) float64 =
+          p^T v = ||d gamma / dt||^2 at every node; ``length`` (B,) float64, the trapezoid of sqrt(speed2) over the steps taken;
+          ``path_head`` (B, S + 1, *x_shape) = g(latents) in the head's input space and ``path``, the same mapped back to data space;
+          ``steps_taken`` (B,) int32; ``info`` (B,) int32, 0 or the first failure code of ``engine.metric_solve``.
+        A trajectory one of whose evaluations fails is frozen at its last good node: its later nodes repeat that node, the other
+        trajectories are unaffected.
+
+        p^T v is conserved wherever G is differentiable, and on tanh-MLP couplers RK4 shows clean fourth order.  ResNet couplers are
+        piecewise linear: J, G and the Hamiltonian jump across ReLU boundaries while an explicit integrator keeps p continuous, so
+        ``speed2`` shows jumps of up to a few per cent that do NOT shrink with the step; ``speed2`` is the record to
+        read.  Sub-batches like a training step; enqueues kernels only -- no copy to the host, no synchronisation -- and leaves
+        ``head.last_gram`` and ``head.last_hutchinson`` alone."""
+        E.require_gpu(z0, "z0")
+        steps = self.shoot_steps if steps is None else int(steps)
+        prog = self.head.program
+        if z0.dim() != 2 or z0.shape[1] != prog.d or not isinstance(v0, torch.Tensor) or v0.shape != z0.shape or \
+                v0.device != z0.device or not v0.is_floating_point():
+            raise ValueError(f"z0 {tuple(z0.shape)} on {z0.device} and v0 {tuple(getattr(v0, 'shape', ()))} on "
+                             f"{getattr(v0, 'device', type(v0).__name__)} must both be (B, {prog.d})")
+        B = z0.shape[0]
+        if B == 0 or steps < 1:
+            raise ValueError(f"shoot needs at least one trajectory and steps >= 1, got {B} trajectories and steps = {steps}")
+        time = float(time)
+        if not (math.isfinite(time) and time > 0):
+            raise ValueError(f"shoot needs a finite time > 0, got {time}")
+        dev = z0.device
+        free = torch.cuda.mem_get_info(dev)[0] + torch.cuda.memory_reserved(dev) - torch.cuda.memory_allocated(dev)
+        chunk = max(1, min(prog.tangent_chunk(B), int(0.8 * free // max(prog.train_bytes_per_sample(16), 1))))
+        grads = E.GradPool([q for q in self.head.parameters() if q.requires_grad], dev)
+        v0 = v0.double().contiguous()
+        with E.scope(self.head.kernels):
+            parts = [self._shoot(z0[i:i + chunk].contiguous(), v0[i:i + chunk], steps, time, grads) for i in range(0, B, chunk)]
+        return parts[0] if len(parts) == 1 else {k: torch.cat([p[k] for p in parts]) for k in parts[0]}
+
+    def _shoot(self, z0, v0, steps, time, grads):
+        B, dev, h = z0.shape[0], z0.device, time / steps
+        z = z0.double()
+        first = self._metric(z0)
+        mom = E.metric_solve(first[2], v0, apply=True)                          # p_0 = G(z_0) v_0
+        p = mom.out64
+        dp, v, s2, info, x_hat = self.shoot_evaluate(z0, p, grads, metric=first)
+        del first
+        alive = info == 0
+        taken = torch.zeros(B, dtype=torch.int32, device=dev)
+        wide = (B,) + (1,) * (x_hat.dim() - 1)
+        nodes = [(z.float(), v, p, s2, x_hat)]
+        for i in range(steps):
+            # the node's own evaluation is the first stage; three more, then the evaluation of the new node
+            codes, kz, kp = [], [v], [dp]
+            for a in (0.5, 0.5, 1.0):
+                dpa, va, _, ia, _ = self.shoot_evaluate((z + (a * h) * kz[-1]).float(), p + (a * h) * kp[-1], grads)
+                kz.append(va)
+                kp.append(dpa)
+                codes.append(ia)
+            z_new = z + (h / 6.0) * (kz[0] + 2.0 * kz[1] + 2.0 * kz[2] + kz[3])
+            p_new = p + (h / 6.0) * (kp[0] + 2.0 * kp[1] + 2.0 * kp[2] + kp[3])
+            # the closing evaluation gives the speed at the last node and needs no backward
+            dp_new, v_new, s2_new, i_new, x_new = self.shoot_evaluate(z_new.float(), p_new, grads, backward=i + 1 < steps)
+            codes.append(i_new)
+            code = codes[3]
+            for c in reversed(codes[:3]):                                       # the first failure code of the step
+                code = torch.where(c != 0, c, code)
+            ok = alive & (code == 0)
+            info = torch.where(alive & ~ok, code, info)
+            z, p = torch.where(ok[:, None], z_new, z), torch.where(ok[:, None], p_new, p)
+            v, s2 = torch.where(ok[:, None], v_new, v), torch.where(ok, s2_new, s2)
+            if dp_new is not None:
+                dp = torch.where(ok[:, None], dp_new, dp)
+            x_hat = torch.where(ok.view(wide), x_new, x_hat)
+            alive = ok
+            taken += ok
+            nodes.append((z.float(), v, p, s2, x_hat))
+        latents, velocity, momentum, speed2, path_head = (torch.stack(t, 1) for t in zip(*nodes))
+        speed = speed2.sqrt()
+        done = torch.arange(steps, device=dev)[None, :] < taken[:, None]        # the steps a trajectory has taken
+        length = h * torch.where(done, 0.5 * (speed[:, :-1] + speed[:, 1:]), torch.zeros_like(speed[:, 1:])).sum(1)
+        x_data = path_head.flatten(0, 1)
+        for bijection in reversed(self.chain):
+            x_data = bijection.z_to_x(x_data)["x"]
+        return {"latents": latents, "velocity": velocity, "momentum": momentum, "speed2": speed2, "length": length,
+                "path_head": path_head, "path": x_data.view(B, steps + 1, *x_data.shape[1:]), "steps_taken": taken, "info": info}

@@ -494,6 +494,21 @@ long long cmf_curve_step_ws(int d, int points, int curves);
 int cmf_curve_step(const float* t, long long t_b, long long t_r, int n_rows, int nc, int d, int points, int curves,
                    const float* jtj, const float* cross, const float* xhat, const double* damping, double* grad, double* delta,
                    double* stats, double* seg2, int* info, double* ws, long long ws_doubles, void* stream);
+/* The per-sample float64 step of geodesic shooting, on the metric G = J^T J of one sample:
+ *   apply == 0 (solve):  out = G^-1 rhs  (Cholesky of G in LDS, pivots only: the elimination of cmf_gauss_newton_step, undamped);
+ *   apply == 1:          out = G rhs, the symmetric product from the lower triangle.
+ *   jtj [B][d][d] float32: the Gram matrix as one cmf_gram_cholesky attempt leaves it; only the lower triangle i >= j is read,
+ *     nothing is written.  rhs [B][d] float64.
+ *   out64 [B][d] float64;  out32 [B][d] float32, out64 rounded to nearest;
+ *   stats [B][2] float64 = { rhs^T out, max_k |out_k| };
+ *   info [B] int32: 0 ok; 1 (solve only) a pivot of G was not positive and finite (out64, out32 and stats are NaN); 2 a non-finite
+ *     value in the lower triangle of jtj or in rhs (every output is NaN).
+ * A sample's outputs are a function of its own inputs and of d alone: no atomics, independent of B, of its position in the batch
+ * and of the order in which workgroups finish, and they repeat bit for bit.
+ * 1 <= d <= 128 (the float64 matrix lives in LDS), B >= 1, apply 0 or 1, float64 pointers 8-byte aligned, the others 4-byte.
+ * Anything else: CMF_EINVAL.  No allocation, no synchronisation.                                                               */
+int cmf_metric_solve(const float* jtj, const double* rhs, int d, int B, int apply, double* out64, float* out32, double* stats,
+                     int* info, void* stream);
 /* Reverse of the head above for training (autograd through non_square.py:307-308, :280-294, :87-100):
  *   dt(b, r, :) = 2 * t(b, r, :) * (g_logdet[b] * jtj_b^-1 + g_l1off[b] * sign(jtj_b)[i != j]
  *                                   + g_l1diag[b] * sign(jtj_b)[i == j])
