@@ -1254,6 +1254,74 @@ def metric_solve(jtj, rhs, apply=False):
     return r
 
 
+#: widest metric ``transport_chain`` takes, and the vectors of one launch (one column group): the float64 window of a curve --
+#: a matrix and its right-hand sides -- lives in LDS (csrc/transport_step.hip)
+TRANSPORT_MAX_WIDTH = 128
+TRANSPORT_MAX_VECTORS = 16
+
+
+class TransportResult:
+    """Outputs of ``transport_chain`` (all on the device, float64 unless noted) for curves of P points and N = P - 1 segments with m
+    vectors each: ``out`` (curves, P, m, d), the vectors at every point (``out[:, 0]`` = w0); ``fwd`` and ``bwd`` (curves, N, m, d),
+    the two halves of every segment, ``out[:, i + 1]`` = (fwd[:, i] + bwd[:, i]) / 2; ``norm2`` (curves, P, m) = w^T G w; ``info``
+    (curves,) int32 (0 ok; 1 a failed pivot in segment i: fwd / bwd from segment i on and out / norm2 from point i + 1 on NaN; 2
+    non-finite input: everything NaN)."""
+    __slots__ = ("out", "fwd", "bwd", "norm2", "info")
+
+
+def transport_chain(jtj, cross, w0, points):
+    """Parallel transport along curve-major curves of ``points`` points: from the Gram matrices ``jtj``
+    (curves * points, d, d) float32 (one ``gram_cholesky`` attempt; the lower triangles are read), the cross-Gram blocks ``cross``
+    (curves * points - 1, d, d) float32 of neighbouring samples of the stack (block s = J_s^T J_{s+1}; those that straddle two curves
+    are not read) and the vectors ``w0`` (curves, m, d) float64 at the first points, in float64 per segment: fwd = G_{i+1}^-1 C_i^T w,
+    bwd = C_i^-1 G_i w, w <- (fwd + bwd) / 2.  Returns a ``TransportResult``.  Deterministic per curve; one launch, no
+    synchronisation."""
+    for name, v in (("jtj", jtj), ("cross", cross), ("w0", w0)):
+        if not isinstance(v, torch.Tensor) or not v.is_cuda:
+            raise ValueError(f"{name} must be on the GPU, got {getattr(v, 'device', type(v).__name__)} (there is no CPU fallback)")
+        want = torch.float64 if name == "w0" else torch.float32
+        if v.dtype != want:
+            raise ValueError(f"{name} must be {str(want).split('.')[1]}, got {v.dtype}")
+    if jtj.dim() != 3 or jtj.shape[1] != jtj.shape[2] or not jtj.is_contiguous():
+        raise ValueError(f"jtj must be a contiguous (curves * points, d, d) tensor, got {tuple(jtj.shape)}"
+                         f"{'' if jtj.is_contiguous() else ' (not contiguous)'}")
+    d, dev, points = jtj.shape[1], jtj.device, int(points)
+    if not 1 <= d <= TRANSPORT_MAX_WIDTH:
+        raise ValueError(f"d = {d}: the transport kernel supports 1 <= d <= {TRANSPORT_MAX_WIDTH}")
+    if points < 2 or jtj.shape[0] % points:
+        raise ValueError(f"points = {points}: a curve needs points >= 2, and the {jtj.shape[0]} samples of jtj must be whole curves")
+    curves = jtj.shape[0] // points
+    if w0.dim() != 3 or w0.shape[0] != curves or w0.shape[2] != d or w0.device != dev or not w0.is_contiguous():
+        raise ValueError(f"w0 must be a contiguous ({curves}, m, {d}) tensor on {dev}, got {tuple(w0.shape)} on {w0.device}"
+                         f"{'' if w0.is_contiguous() else ' (not contiguous)'}")
+    m = w0.shape[1]
+    if not 1 <= m <= TRANSPORT_MAX_VECTORS:
+        raise ValueError(f"m = {m}: the transport kernel takes 1 <= m <= {TRANSPORT_MAX_VECTORS} vectors per launch")
+    if cross.shape != (max(curves * points - 1, 0), d, d) or cross.device != dev or not cross.is_contiguous():
+        raise ValueError(f"cross must be a contiguous ({max(curves * points - 1, 0)}, {d}, {d}) tensor on {dev}, got "
+                         f"{tuple(cross.shape)} on {cross.device}{'' if cross.is_contiguous() else ' (not contiguous)'}")
+    r = TransportResult()
+    r.out = torch.empty(curves, points, m, d, dtype=torch.float64, device=dev)
+    r.fwd = torch.empty(curves, points - 1, m, d, dtype=torch.float64, device=dev)
+    r.bwd = torch.empty(curves, points - 1, m, d, dtype=torch.float64, device=dev)
+    r.norm2 = torch.empty(curves, points, m, dtype=torch.float64, device=dev)
+    r.info = torch.empty(curves, dtype=torch.int32, device=dev)
+    if curves == 0:
+        return r
+    launch = lambda: _lib.check(_lib.load().cmf_transport_chain(_p(jtj), _p(cross), _p(w0), d, m, points, curves, _p(r.out), _p(r.fwd),
+                                                                _p(r.bwd), _p(r.norm2), _p(r.info), _stream()), "cmf_transport_chain")
+    TIMER = _timer()
+    if TIMER is None:
+        launch()
+    else:
+        # float64 per segment: the LU 2 d^3 / 3 and the Cholesky d^3 / 3 with their right-hand sides 3 m d^2 and the substitutions
+        # 3 m d^2, the two products 4 m d^2; bytes: jtj three times (the check, the product, the triangle), cross three times, the outputs
+        N = points - 1
+        TIMER.wrap("transport_chain", curves * (N * (d ** 3 + 10.0 * m * d * d) + 2.0 * points * m * d * d),
+                   curves * (12.0 * (points + N) * d * d + 8.0 * (points + 2 * N) * m * d + 8.0 * m * d + 8.0 * points * m + 4.0), launch)
+    return r
+
+
 def gram_backward(T, jtj, g_logdet=None, g_l1off=None, g_l1diag=None):
     """Cotangent of the Jacobian stack T for a loss with d/d logdet = g_logdet, d/d l1_off = g_l1off, d/d l1_diag =
     g_l1diag (each (B,) or None): what autograd yields through non_square.py:307-308, :280-294, :87-100."""

@@ -18,6 +18,14 @@ per-sample float64 solve (csrc/shoot_step.hip), a one-direction sweep that is ke
     lg = geo.log(x0, x1)                                 # connect + the initial velocity of the relaxed curve
     out = geo.shoot(x0, lg["velocity"])                  # out["path"][:, -1] is close to x1
     out = geo.shoot_latents(z0, v0, steps=8, time=0.5)
+
+``transport`` is parallel transport: a latent tangent direction at one input carried along the geodesic to another,
+keeping its length and its angles in the pull-back metric.  Per segment it averages the projection onto the next tangent plane
+with the inverse of the projection back (csrc/transport_step.hip, float64 per curve), which is second order in the segment.
+
+    tr = geo.transport(x0, x1, w)                        # connect + w (B, d) or (B, d, m) at x0 carried to x1
+    tr["transported"], tr["norm2"]                       # (B, d, m) at x1; w^T G w at every point of the curve
+    out = geo.analogy(xa, xb, xc)                        # "a is to b as c is to ?": out["path"][:, -1]
 """
 import math
 
@@ -39,7 +47,10 @@ class ManifoldGeodesic:
     therefore monotone non-increasing, and ``steps=0`` gives the diagnostics of the straight latent line.
 
     ``shoot`` / ``shoot_latents`` integrate the geodesic that leaves a point with a given latent velocity in ``shoot_steps`` >= 1
-    RK4 steps (``log`` / ``log_latents``: ``connect`` plus the velocity that takes ``shoot`` from the first end to the second)."""
+    RK4 steps (``log`` / ``log_latents``: ``connect`` plus the velocity that takes ``shoot`` from the first end to the second).
+
+    ``transport`` / ``transport_latents`` carry latent tangent vectors along a curve by parallel transport; ``analogy`` carries the
+    ``log`` velocity of one pair of inputs to a third input and shoots along it there."""
 
     def __init__(self, density, points=17, steps=10, damping=1e-3, up=10.0, down=0.1, shoot_steps=16):
         if int(shoot_steps) < 1:
@@ -297,3 +308,95 @@ class ManifoldGeodesic:
             x_data = bijection.z_to_x(x_data)["x"]
         return {"latents": latents, "velocity": velocity, "momentum": momentum, "speed2": speed2, "length": length,
                 "path_head": path_head, "path": x_data.view(B, steps + 1, *x_data.shape[1:]), "steps_taken": taken, "info": info}
+
+    # -- parallel transport --------------------------------------------------------------------
+    @torch.no_grad()
+    def transport_latents(self, latents, w):
+        """Carry the latent tangent vectors ``w`` ((B, d) or (B, d, m), any m >= 1, floating point: components at point 0) along
+        the curves ``latents`` (B, P, d) float32 of the head's latents, P >= 2 -- any curves, they need not be geodesics -- by
+        parallel transport in the pull-back metric G = J^T J.  Per segment, with C_i = J_i^T J_{i+1}, in float64:
+        forward = G_{i+1}^-1 C_i^T w_i (the projection onto the next tangent plane), backward = C_i^-1 G_i w_i (the inverse of the
+        projection back), w_{i+1} = (forward + backward) / 2: the rotation between the two planes up to the fourth power of the
+        angle between them.  Returns device tensors for the B curves of N = P - 1 segments:
+          ``vectors`` (B, P, d, m) float64, the components at every point (``vectors[:, 0]`` = w); ``forward`` and ``backward``
+          (B, N, d, m) float64 -- their gap shows how far the tangent plane turned in a segment; ``norm2`` (B, P, m) float64 =
+          w_i^T G_i w_i, which parallel transport keeps; ``info`` (B,) int32: 0, 1 where a pivot of some G_{i+1} or C_i failed in
+          segment i (``forward`` / ``backward`` from that segment on and ``vectors`` / ``norm2`` from point i + 1 on are NaN), 2
+          where an input was not finite (everything NaN); the other curves are unaffected.  A (B, d) ``w`` gives m = 1.
+        One decode sweep with tangents over every point -- in sub-batches of whole curves, each padded with a copy of its first and
+        of its last point so that one ``engine.cross_gram`` call yields every in-curve block --, the Gram and cross-Gram launches
+        and ``engine.transport_chain`` once per group of 16 vectors; enqueues kernels only -- no copy to the host, no
+        synchronisation -- and leaves ``head.last_gram`` alone.  On ReLU couplers the manifold is piecewise linear: nothing
+        converges with P there, the scheme just stays well behaved."""
+        E.require_gpu(latents, "latents")
+        prog = self.head.program
+        d = prog.d
+        if latents.dim() != 3 or latents.shape[2] != d or latents.shape[1] < 2:
+            raise ValueError(f"latents {tuple(latents.shape)} must be (B, points >= 2, {d})")
+        B, P = latents.shape[0], latents.shape[1]
+        if not isinstance(w, torch.Tensor) or not w.is_floating_point() or w.device != latents.device or w.dim() not in (2, 3) or \
+                w.shape[:2] != (B, d) or (w.dim() == 3 and w.shape[2] < 1):
+            raise ValueError(f"w {tuple(getattr(w, 'shape', ()))} on {getattr(w, 'device', type(w).__name__)} must be ({B}, {d}) or "
+                             f"({B}, {d}, m >= 1) floating point on {latents.device}")
+        if B == 0:
+            raise ValueError("transport needs at least one curve")
+        w0 = (w[:, :, None] if w.dim() == 2 else w).double().transpose(1, 2).contiguous()       # (B, m, d)
+        chunk = (prog.tangent_chunk(B * P + 2) - 2) // P
+        if chunk <= 0:
+            raise ValueError(f"points = {P}: one curve of {P} points and its two padding samples do not fit the sub-batch of "
+                             f"{prog.tangent_chunk(B * P + 2)} samples a decode sweep may hold; use fewer points")
+        with E.scope(self.head.kernels):
+            parts = [self._transport(latents[i:i + chunk], w0[i:i + chunk]) for i in range(0, B, chunk)]
+        return parts[0] if len(parts) == 1 else {k: torch.cat([p[k] for p in parts]) for k in parts[0]}
+
+    def _transport(self, latents, w0):
+        prog = self.head.program
+        B, P, d = latents.shape
+        m = w0.shape[1]
+        flat = latents.reshape(B * P, d)
+        # one "curve" of B P + 2 points: its B P - 1 interior pairs are the pairs (s, s + 1) of the curve-major stack
+        padded = torch.cat([flat[:1], flat, flat[-1:]])
+        _, T = prog.decode(padded, tangents=True)
+        jtj = E.gram_cholesky(T, d, 1).jtj[1:-1]
+        cross = E.cross_gram(T, d, B * P + 2)[0]
+        del T
+        groups = [E.transport_chain(jtj, cross, w0[:, j:j + E.TRANSPORT_MAX_VECTORS].contiguous(), P)
+                  for j in range(0, m, E.TRANSPORT_MAX_VECTORS)]
+        join = lambda name: torch.cat([getattr(r, name) for r in groups], 2).transpose(2, 3).contiguous()
+        out = {"vectors": join("out"), "forward": join("fwd"), "backward": join("bwd"),
+               "norm2": torch.cat([r.norm2 for r in groups], 2), "info": groups[0].info}
+        if len(groups) > 1:
+            # the groups share the matrices, so they agree on code 1; a non-finite vector in one group is code 2 for the whole curve
+            for r in groups[1:]:
+                out["info"] = torch.maximum(out["info"], r.info)
+            bad = out["info"] == 2
+            for key in ("vectors", "forward", "backward", "norm2"):
+                t = out[key]
+                out[key] = torch.where(bad.view(-1, *([1] * (t.dim() - 1))), torch.full_like(t, float("nan")), t)
+        return out
+
+    @torch.no_grad()
+    def transport(self, x0, x1, w, steps=None):
+        """``connect(x0, x1, steps)`` and ``transport_latents`` of ``w`` ((B, d) or (B, d, m): latent components at ``x0``) along
+        its relaxed ``latents``: the values of ``connect``, unchanged, beside ``vectors``, ``forward``, ``backward``, ``norm2``,
+        ``transport_info`` (the ``info`` of ``transport_latents``; ``info`` stays ``connect``'s) and ``transported`` (B, d, m)
+        float64 = ``vectors[:, -1]``, the components at ``x1``."""
+        out = dict(self.connect(x0, x1, steps))
+        tr = self.transport_latents(out["latents"], w)
+        tr["transport_info"] = tr.pop("info")
+        out.update(tr)
+        out["transported"] = tr["vectors"][:, -1]
+        return out
+
+    @torch.no_grad()
+    def analogy(self, xa, xb, xc, steps=None, shoot_steps=None, time=1.0):
+        """"``xa`` is to ``xb`` as ``xc`` is to ?": the velocity v = ``log(xa, xb)["velocity"]`` that walks from ``xa`` to ``xb``
+        is carried along the geodesic from ``xa`` to ``xc`` by ``transport`` and ``shoot``s from ``xc`` for ``time``.  Returns the
+        values of ``shoot`` (``path[:, -1]`` is the answer in data space) beside ``velocity`` (B, d) float64, ``transported``
+        (B, d) float64 -- that velocity at ``xc`` -- and ``transport_info`` (B,) int32."""
+        v = self.log(xa, xb, steps)["velocity"]
+        tr = self.transport(xa, xc, v, steps)
+        moved = tr["transported"][:, :, 0].contiguous()
+        out = dict(self.shoot(xc, moved, shoot_steps, time))
+        out.update(velocity=v, transported=moved, transport_info=tr["transport_info"])
+        return out

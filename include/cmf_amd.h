@@ -509,6 +509,27 @@ int cmf_curve_step(const float* t, long long t_b, long long t_r, int n_rows, int
  * Anything else: CMF_EINVAL.  No allocation, no synchronisation.                                                               */
 int cmf_metric_solve(const float* jtj, const double* rhs, int d, int B, int apply, double* out64, float* out32, double* stats,
                      int* info, void* stream);
+/* Parallel transport of m latent tangent vectors along discretised curves.  A curve has `points` = P >= 2 points and
+ * N = P - 1 segments; samples are curve-major: point i of curve c is sample c P + i.  With G_i = J_i^T J_i and C_i = J_i^T J_{i+1},
+ * per curve and per vector in float64 (no contraction), segment by segment:
+ *   fwd_i = G_{i+1}^-1 (C_i^T w_i)   (Cholesky of G_{i+1} in LDS, pivots only: the elimination of cmf_metric_solve);
+ *   bwd_i = C_i^-1 (G_i w_i)         (Gaussian elimination with partial pivoting: the pivot of a column is its largest |entry|, the
+ *                                     lowest row among equals; multipliers by division);
+ *   w_{i+1} = 0.5 (fwd_i + bwd_i);   norm2_i = w_i^T G_i w_i = sum_r w_r (sum_j G_rj w_j), j and r ascending.
+ *   jtj [curves P][d][d] float32 as ONE cmf_gram_cholesky attempt leaves it: the lower triangles are read, nothing is written.
+ *   cross [curves P - 1][d][d] float32: block s = J_s^T J_{s+1} over the sample stack, the whole (unsymmetric) block; the blocks
+ *     s = c P - 1 straddle two curves and are never read.  w0 [curves][m][d] float64.
+ *   out [curves][P][m][d] float64, out[c][0] = w0[c];  fwd, bwd [curves][N][m][d];  norm2 [curves][P][m].
+ *   info [curves] int32: 0 ok; 1 a pivot of some G_{i+1} was not positive and finite or a pivot of some C_i was zero or not finite
+ *     (fwd and bwd of segment i and of the later segments, out and norm2 from point i + 1 on are NaN; everything before keeps the
+ *     bits it would have had); 2 a non-finite value in w0 or in a part of jtj / cross that is read (every output of the curve is
+ *     NaN; takes precedence over 1).
+ * A curve's outputs are a function of its own inputs and of (d, m, P) alone: no atomics, independent of `curves`, of the curve's
+ * position and of completion order, and they repeat bit for bit.
+ * 1 <= d <= 128, 1 <= m <= 16 (the float64 window lives in LDS), P >= 2, curves >= 1, no pointer NULL, float64 pointers 8-byte
+ * aligned, the others 4-byte.  Anything else: CMF_EINVAL.  No allocation, no synchronisation.                                  */
+int cmf_transport_chain(const float* jtj, const float* cross, const double* w0, int d, int m, int points, int curves, double* out,
+                        double* fwd, double* bwd, double* norm2, int* info, void* stream);
 /* Reverse of the head above for training (autograd through non_square.py:307-308, :280-294, :87-100):
  *   dt(b, r, :) = 2 * t(b, r, :) * (g_logdet[b] * jtj_b^-1 + g_l1off[b] * sign(jtj_b)[i != j]
  *                                   + g_l1diag[b] * sign(jtj_b)[i == j])
