@@ -41,7 +41,9 @@ def _digest(paths):
 
 def build(force=False, verbose=True):
     srcs = sorted(os.path.join(CSRC, f) for f in os.listdir(CSRC) if f.endswith(".hip"))
-    deps = srcs + [os.path.join(CSRC, "common.h"), os.path.join(ROOT, "include", "cmf_amd.h")]
+    # every header under csrc: an edit to one that the list missed would leave the stale library in use, silently
+    headers = sorted(os.path.join(CSRC, f) for f in os.listdir(CSRC) if f.endswith(".h"))
+    deps = srcs + headers + [os.path.join(ROOT, "include", "cmf_amd.h")]
     stamp = os.path.join(OBJ, "stamp")
     dig = _digest(deps)
     if not force and os.path.exists(LIB) and os.path.exists(stamp) and open(stamp).read() == dig:

@@ -13,31 +13,31 @@
 // cmf_curve_step: one 256-thread workgroup per curve, everything in float64, nothing shared between workgroups, no atomics.
 //   1. ||r_i||^2 per segment: thread t sums rows t, t + 256, ..., folded by a fixed binary tree; their sum in segment order.
 //      The energy-only launch (t == NULL) is this phase alone, so both modes give the same bits.
-//   2. g_i = J_i^T s_i streams J_i once per interior point, as phase 2 of gn_step.hip, with the second difference
-//      s = (xhat_{i-1} + xhat_{i+1}) - 2 xhat_i formed in float64 on the fly.  Then the lower triangles of jtj and the cross blocks
-//      are scanned for non-finite values (info 2 takes precedence over a failed pivot).
+//   2. g_i = J_i^T s_i streams J_i once per interior point, as phase 2 of gn_step.hip (dense_f64.h, jt_stream), with the second
+//      difference s = (xhat_{i-1} + xhat_{i+1}) - 2 xhat_i formed in float64 on the fly.  Then the lower triangles of jtj and the
+//      cross blocks are scanned for non-finite values (info 2 takes precedence over a failed pivot).
 //   3. Block elimination on a window of 2 d + 1 rows: [S_i, . ; -C_i^T, 2 G_{i+1} (1 + lambda on the diagonal)] with the g entries of
 //      the two blocks as the extra row.  The d columns of block i are eliminated by the pivot-only elimination of gn_step.hip
-//      (A_rj -= (A_rk / p_k) A_jk on the lower triangle, multipliers by division, one barrier per column); that leaves the Schur
+//      (dense_f64.h, eliminate: d columns of a triangle of extent 2 d, the extra row parked at row 2 d); that leaves the Schur
 //      complement S_{i+1} and the forward-substituted g_{i+1} in the lower right, which move to the upper left for the next block.
 //      The finished columns (unscaled multipliers, pivots, w_k = y_k L_kk) go to the curve's workspace slice.
 //      The window (row stride 2 d + 1: odd) lives in LDS for d <= 64 and in the workspace slice for 64 < d <= 128, where only the
 //      owning workgroup touches it and the barriers order the steps.
 //   4. Back substitution, last block first: the d x d triangle of a block comes back into LDS, the coupling to the block after it
-//      is folded into w by one thread per column, then delta_k = (w_k - sum_{r > k} A_rk delta_r) / p_k with one barrier per column.
+//      is folded into w by one thread per column, then the back substitution of dense_f64.h.
 //      delta^T H delta is summed on the way from the float32 inputs (the window no longer holds H), g^T delta and max |g| alike.
 // No fused multiply-adds (fp contract off): every operation is one correctly rounded float64 operation, those of a plain float64
 // emulation of the same sequence.
 //
 // info: 0 ok; 1 a pivot that is not positive and finite (delta, stats[1], stats[2] = NaN; the rest valid); 2 a non-finite value
 // in xhat, the first d columns of an interior point's t, the lower triangle of an interior jtj or a cross block (every output NaN).
-#include "common.h"
-
 #pragma clang fp contract(off)
+#include "dense_f64.h"                             // after the pragma: the helpers are compiled without contraction
 
 namespace {
 
 constexpr int NT = 256;
+static_assert(NT == F64_NT, "dense_f64.h is written for this workgroup size");
 constexpr int MAXD = 128;
 constexpr int LDS_MAXD = 64;                      // widest d whose window sits in LDS
 constexpr int PART = 4 * NT;                      // doubles: the J^T s partials [row group][4 LP]; the trees use the first NT
@@ -47,8 +47,6 @@ constexpr int KC = 32;                            // J rows per LDS slab of the 
 inline __host__ __device__ int window_stride(int d) { return 2 * d + 1; }
 inline __host__ __device__ long long save_doubles(int d) { return (long long)(2 * d + 1) * d; }
 inline __host__ __device__ long long window_doubles(int d) { return d > LDS_MAXD ? (long long)(2 * d + 1) * window_stride(d) : 0; }
-
-__device__ __forceinline__ bool not_finite(float v) { return !(fabsf(v) <= __FLT_MAX__); }
 
 // C = Ja^T Jb for one pair of neighbouring points: NTL x NTL tiles of 16 x 16, wave w owns the row tiles w, w + 4.
 template <int NTL>
@@ -157,25 +155,6 @@ int launch_cross(const float* t, long long t_b, long long t_r, int n_rows, int d
   return 0;
 }
 
-// Fold one value per thread by a fixed binary tree (sum, or maximum with MAX); the result in every thread.  part: NT doubles
-// that nobody else touches between the two barriers that bracket the call.
-template <bool MAX>
-__device__ __forceinline__ double block_fold(double v, double* part) {
-  const int tid = threadIdx.x;
-  part[tid] = v;
-  __syncthreads();
-  for (int s = NT / 2; s > 0; s >>= 1) {
-    if (tid < s) {
-      const double a = part[tid], c = part[tid + s];
-      part[tid] = MAX ? (c > a ? c : a) : a + c;
-    }
-    __syncthreads();
-  }
-  const double out = part[0];
-  __syncthreads();                                // part may be rewritten by the caller
-  return out;
-}
-
 // MODE 0: energy only; 1: the window in LDS (d <= 64); 2: the window in the workspace slice
 template <int MODE>
 __global__ __launch_bounds__(NT) void curve_step_kernel(const float* __restrict__ t, long long t_b, long long t_r, int n_rows, int d,
@@ -225,42 +204,21 @@ __global__ __launch_bounds__(NT) void curve_step_kernel(const float* __restrict_
 
   // 2. g_i = J_i^T s_i for the interior points; thread k < d keeps g_ik in turn and the running max |g_ik|
   double gmax = 0.0;
-  {
-    const int lane = tid & (LP - 1), rg = tid / LP, RG = NT / LP, c0 = 4 * lane;
-    const bool m1 = c0 + 1 < d, m2 = c0 + 2 < d, m3 = c0 + 3 < d;
-    for (int i = 1; i <= M; ++i) {
-      double a0 = 0.0, a1 = 0.0, a2 = 0.0, a3 = 0.0;
-      if (c0 < d) {                                // c0 + 3 < nc: nc is a multiple of 16 and >= d
-        const float* __restrict__ tp = t + (c * P + i) * t_b + c0;
-        const float* __restrict__ x0 = xc + (long long)i * n_rows;
-        const float* __restrict__ xm = x0 - n_rows;
-        const float* __restrict__ xp = x0 + n_rows;
-#pragma unroll 4
-        for (int r = rg; r < n_rows; r += RG) {
-          const f32x4 v = *(const f32x4*)(tp + (long long)r * t_r);
-          const double s = ((double)xm[r] + (double)xp[r]) - 2.0 * (double)x0[r];
-          bad |= not_finite(v.x) | (m1 & not_finite(v.y)) | (m2 & not_finite(v.z)) | (m3 & not_finite(v.w));
-          a0 += (double)v.x * s;
-          a1 += (double)v.y * s;
-          a2 += (double)v.z * s;
-          a3 += (double)v.w * s;
-        }
-      }
-      double* p = part + rg * (4 * LP) + c0;       // < PART: rg < RG, c0 + 3 < 4 LP
-      p[0] = a0;
-      p[1] = a1;
-      p[2] = a2;
-      p[3] = a3;
-      __syncthreads();
-      if (tid < d) {
-        double gk = 0.0;
-        for (int q = 0; q < RG; ++q) gk += part[q * (4 * LP) + tid];
-        gc[(long long)(i - 1) * d + tid] = gk;     // read back by this same thread only
-        const double ag = fabs(gk);
-        gmax = ag > gmax ? ag : gmax;
-      }
-      __syncthreads();
+  for (int i = 1; i <= M; ++i) {
+    const float* __restrict__ x0 = xc + (long long)i * n_rows;
+    const float* __restrict__ xm = x0 - n_rows;
+    const float* __restrict__ xp = x0 + n_rows;
+    jt_stream(t + (c * P + i) * t_b, t_r, n_rows, d, LP, part,
+              [=](int r) { return ((double)xm[r] + (double)xp[r]) - 2.0 * (double)x0[r]; }, bad);
+    __syncthreads();
+    if (tid < d) {
+      double gk = 0.0;
+      for (int q = 0; q < NT / LP; ++q) gk += part[q * (4 * LP) + tid];
+      gc[(long long)(i - 1) * d + tid] = gk;       // read back by this same thread only
+      const double ag = fabs(gk);
+      gmax = ag > gmax ? ag : gmax;
     }
+    __syncthreads();
   }
   // the parts of jtj and cross that are read
   for (int i = 1; i <= M; ++i) {
@@ -310,9 +268,8 @@ __global__ __launch_bounds__(NT) void curve_step_kernel(const float* __restrict_
     if (tid < d) W[R * LD + o + tid] = gc[(long long)(i - 1) * d + tid];
   };
   load_block(1, 0);
-  const int ti = tid >> 4, tj = tid & 15;
   int fail = 0;
-  for (int i = 1; i <= M && !fail; ++i) {
+  for (int i = 1; i <= M; ++i) {
     const bool last = i == M;
     const int nw = last ? d : 2 * d;
     if (!last) {
@@ -324,20 +281,7 @@ __global__ __launch_bounds__(NT) void curve_step_kernel(const float* __restrict_
       load_block(i + 1, d);
     }
     __syncthreads();
-    for (int k = 0; k < d; ++k) {
-      const double piv = W[k * LD + k];             // uniform
-      if (!(piv > 0.0) || !(piv < 1.0e300)) {
-        fail = 1;
-        break;
-      }
-      for (int r = k + 1 + ti; r <= nw; r += 16) {
-        double* row = W + (r < nw ? r : R) * LD;
-        const double ark = row[k] / piv;            // a division: x / x = 1, exact cancellation stays exact
-        const int jmax = r < nw ? r : nw - 1;
-        for (int j = k + 1 + tj; j <= jmax; j += 16) row[j] -= ark * W[j * LD + k];
-      }
-      __syncthreads();
-    }
+    fail = eliminate(W, LD, d, nw, R, 1);
     if (fail) break;                                // uniform
     // the finished columns: rows 0 .. nw - 1 and the extra row (as row 2 d), columns 0 .. d - 1
     double* Ls = wsc + (long long)(i - 1) * SAVE;
@@ -385,12 +329,7 @@ __global__ __launch_bounds__(NT) void curve_step_kernel(const float* __restrict_
       wv[tid] = Ls[(long long)R * d + tid] - acc;
     }
     __syncthreads();
-    for (int a = d - 1; a >= 0; --a) {
-      const double da = wv[a] / A[a * LT + a];
-      if (tid < a) wv[tid] -= A[a * LT + tid] * da;
-      if (tid == a) dcur[a] = da;
-      __syncthreads();
-    }
+    back_substitute(A, LT, d, wv, dcur);
     if (tid < d) {
       const double dk = dcur[tid];
       dc[(long long)(i - 1) * d + tid] = dk;

@@ -16,46 +16,25 @@
 //   3. The lower triangle of G is loaded into the float64 matrix A in LDS, with g as row d below it, and the diagonal is scaled
 //      by 1 + lambda.  The row stride is d | 1: odd, so that the column reads of the elimination (16 rows of one column per
 //      wave) spread over the banks instead of landing on one.
-//   4. Cholesky without square roots on the lower triangle (the elimination of gram_cond.hip): A_ij -= A_ik A_jk / p_k for
-//      k < j <= i, one barrier per column; the pivots p_k land on the diagonal, column k keeps the unscaled multipliers
-//      L_ik L_kk.  Row d takes part like any other row, which IS the forward substitution: it ends as w_k = y_k L_kk, L y = g.
-//   5. Back substitution on row d, last column first: delta_i = (w_i - sum_{k > i} A_ki delta_k) / p_i, one barrier per column.
+//   4. Cholesky without square roots on the lower triangle with g as the extra row d (dense_f64.h, eliminate): the pivots p_k
+//      land on the diagonal, row d ends forward-substituted.
+//   5. Back substitution on row d (dense_f64.h, back_substitute).
 //   6. delta^T G delta from the float32 lower triangle in global memory (A no longer holds G): sum of G_ii delta_i^2 and
 //      2 G_ij delta_i delta_j over i > j, element e of the matrix to thread e mod 256, tree-folded; g^T delta and max |g_k| alike.
 //
 // info: 0 ok; 1 a pivot that is not positive and finite (delta, stats[1], stats[2] = NaN; grad, stats[0], stats[3] valid);
 // 2 a non-finite value in x, x_hat, the first d columns of t or the lower triangle of jtj (every output NaN).
-#include "common.h"
+#include "dense_f64.h"                             // no fp-contract pragma in this file: the helpers fuse multiply-adds
 
 namespace {
 
 constexpr int NT = 256;
+static_assert(NT == F64_NT, "dense_f64.h is written for this workgroup size");
 constexpr int MAXD = 128;
 constexpr int PART = 4 * NT;                      // doubles: the J^T r partials [row group][4 LP]; the trees use the first NT
 constexpr int SMALL = PART + MAXD;                // + delta [MAXD]; then A [(d + 1) * row_stride(d)]
 
 inline __host__ __device__ int row_stride(int d) { return d | 1; }
-
-__device__ __forceinline__ bool not_finite(float v) { return !(fabsf(v) <= __FLT_MAX__); }
-
-// Fold one value per thread by a fixed binary tree (sum, or maximum with MAX); the result in every thread.  part: NT doubles
-// that nobody else touches between the two barriers that bracket the call.
-template <bool MAX>
-__device__ __forceinline__ double block_fold(double v, double* part) {
-  const int tid = threadIdx.x;
-  part[tid] = v;
-  __syncthreads();
-  for (int s = NT / 2; s > 0; s >>= 1) {
-    if (tid < s) {
-      const double a = part[tid], c = part[tid + s];
-      part[tid] = MAX ? (c > a ? c : a) : a + c;
-    }
-    __syncthreads();
-  }
-  const double out = part[0];
-  __syncthreads();                                // part may be rewritten by the caller
-  return out;
-}
 
 template <bool FULL>
 __global__ __launch_bounds__(NT) void gn_step_kernel(const float* __restrict__ t, long long t_b, long long t_r, int n_rows, int d,
@@ -93,41 +72,12 @@ __global__ __launch_bounds__(NT) void gn_step_kernel(const float* __restrict__ t
   double* dl = lds + PART;                        // [MAXD]
   double* A = lds + SMALL;                        // [(d + 1) * LD]
   const int LD = row_stride(d);
-  {
-    const int lane = tid & (LP - 1), rg = tid / LP, RG = NT / LP, c0 = 4 * lane;
-    double a0 = 0.0, a1 = 0.0, a2 = 0.0, a3 = 0.0;
-    if (c0 < d) {                                 // c0 + 3 < nc: nc is a multiple of 16 and >= d
-      const bool m1 = c0 + 1 < d, m2 = c0 + 2 < d, m3 = c0 + 3 < d;
-      const float* __restrict__ tp = t + (long long)b * t_b + c0;
-#pragma unroll 4
-      for (int r = rg; r < n_rows; r += RG) {
-        const f32x4 v = *(const f32x4*)(tp + (long long)r * t_r);
-        const double rr = (double)xb[r] - (double)hb[r];
-        bad |= not_finite(v.x) | (m1 & not_finite(v.y)) | (m2 & not_finite(v.z)) | (m3 & not_finite(v.w));
-        a0 += (double)v.x * rr;
-        a1 += (double)v.y * rr;
-        a2 += (double)v.z * rr;
-        a3 += (double)v.w * rr;
-      }
-    }
-    double* p = part + rg * (4 * LP) + c0;        // < PART: rg < RG, c0 + 3 < 4 LP
-    p[0] = a0;
-    p[1] = a1;
-    p[2] = a2;
-    p[3] = a3;
-  }
+  jt_stream(t + (long long)b * t_b, t_r, n_rows, d, LP, part, [=](int r) { return (double)xb[r] - (double)hb[r]; }, bad);
 
   // 3. the lower triangle of G
   const int dd = d * d;
   const float* __restrict__ G = jtj + (long long)b * dd;
-  for (int e = tid; e < dd; e += NT) {
-    const int i = e / d, j = e - i * d;
-    if (j <= i) {
-      const float v = G[e];
-      bad |= not_finite(v);
-      A[i * LD + j] = (double)v;
-    }
-  }
+  bad |= load_lower<true>(G, d, A, LD);
   if (__syncthreads_or(bad)) {                    // uniform; the barrier also publishes part and A
     for (int k = tid; k < d; k += NT) {
       grad[(long long)b * d + k] = nan;
@@ -149,21 +99,7 @@ __global__ __launch_bounds__(NT) void gn_step_kernel(const float* __restrict__ t
   __syncthreads();
 
   // 4. pivots and multipliers; row d is g
-  const int ti = tid >> 4, tj = tid & 15;
-  int fail = 0;
-  for (int k = 0; k < d; ++k) {
-    const double piv = A[k * LD + k];             // uniform
-    if (!(piv > 0.0) || !(piv < 1.0e300)) {
-      fail = 1;
-      break;
-    }
-    for (int i = k + 1 + ti; i <= d; i += 16) {
-      const double aik = A[i * LD + k] / piv;      // a division: x / x = 1, a duplicate column cancels its pivot exactly
-      const int jmax = i < d ? i : d - 1;
-      for (int j = k + 1 + tj; j <= jmax; j += 16) A[i * LD + j] -= aik * A[j * LD + k];
-    }
-    __syncthreads();
-  }
+  const int fail = eliminate(A, LD, d, d, d, 1);
   const double gmax = block_fold<true>(tid < d ? fabs(gk) : 0.0, part);
   if (fail) {                                     // uniform
     if (tid < d) delta[(long long)b * d + tid] = nan;
@@ -178,13 +114,7 @@ __global__ __launch_bounds__(NT) void gn_step_kernel(const float* __restrict__ t
   }
 
   // 5. back substitution on row d
-  double* w = A + d * LD;
-  for (int i = d - 1; i >= 0; --i) {
-    const double di = w[i] / A[i * LD + i];
-    if (tid < i) w[tid] -= A[i * LD + tid] * di;
-    if (tid == i) dl[i] = di;
-    __syncthreads();
-  }
+  back_substitute(A, LD, d, A + d * LD, dl);
 
   // 6. the two forms
   double gd = 0.0, q = 0.0;

@@ -10,47 +10,24 @@
 //
 //   1. The lower triangle of G is loaded into the float64 matrix A in LDS, with rhs as row d below it.  The row stride is d | 1:
 //      odd, so that the column reads of the elimination (16 rows of one column per wave) spread over the banks.
-//   2. solve: Cholesky without square roots on the lower triangle -- the elimination of gn_step.hip / gram_cond.hip, restated here
-//      so that those kernels keep their bits: A_ij -= A_ik A_jk / p_k for k < j <= i, one barrier per column; the pivots p_k land
-//      on the diagonal.  Row d takes part like any other row, which IS the forward substitution.  Then the back substitution on row
-//      d, last column first, one barrier per column.
+//   2. solve: Cholesky without square roots on the lower triangle with rhs as the extra row d, which ends forward-substituted,
+//      then the back substitution on row d (dense_f64.h: eliminate, back_substitute -- the elimination of gn_step.hip).
 //      apply: thread i sums A_[max(i,j)][min(i,j)] rhs_j over j = 0 .. d - 1 in that order.
 //   3. rhs^T out and max |out_k|: one value per thread, folded by a fixed binary tree in LDS.
 // The order of every sum is a function of d alone.
 //
 // info: 0 ok; 1 (solve) a pivot that is not positive and finite (out64, out32, stats = NaN); 2 a non-finite value in the lower
 // triangle of jtj or in rhs (every output NaN).
-#include "common.h"
+#include "dense_f64.h"                             // no fp-contract pragma in this file: the helpers fuse multiply-adds
 
 namespace {
 
 constexpr int NT = 256;
+static_assert(NT == F64_NT, "dense_f64.h is written for this workgroup size");
 constexpr int MAXD = 128;
 constexpr int SMALL = NT + MAXD;                  // doubles: the tree's partials [NT], out [MAXD]; then A [(d + 1) * row_stride(d)]
 
 inline __host__ __device__ int row_stride(int d) { return d | 1; }
-
-__device__ __forceinline__ bool not_finite(float v) { return !(fabsf(v) <= __FLT_MAX__); }
-__device__ __forceinline__ bool not_finite(double v) { return !(fabs(v) <= __DBL_MAX__); }
-
-// Fold one value per thread by a fixed binary tree (sum, or maximum with MAX); the result in every thread.  part: NT doubles
-// that nobody else touches between the two barriers that bracket the call.
-template <bool MAX>
-__device__ __forceinline__ double block_fold(double v, double* part) {
-  const int tid = threadIdx.x;
-  part[tid] = v;
-  __syncthreads();
-  for (int s = NT / 2; s > 0; s >>= 1) {
-    if (tid < s) {
-      const double a = part[tid], c = part[tid + s];
-      part[tid] = MAX ? (c > a ? c : a) : a + c;
-    }
-    __syncthreads();
-  }
-  const double out = part[0];
-  __syncthreads();                                // part may be rewritten by the caller
-  return out;
-}
 
 template <bool APPLY>
 __global__ __launch_bounds__(NT) void metric_solve_kernel(const float* __restrict__ jtj, const double* __restrict__ rhs, int d,
@@ -66,16 +43,7 @@ __global__ __launch_bounds__(NT) void metric_solve_kernel(const float* __restric
   const long long ob = (long long)b * d;
 
   // 1. the lower triangle of G, rhs below it
-  int bad = 0;
-  const float* __restrict__ G = jtj + (long long)b * dd;
-  for (int e = tid; e < dd; e += NT) {
-    const int i = e / d, j = e - i * d;
-    if (j <= i) {
-      const float v = G[e];
-      bad |= not_finite(v);
-      A[i * LD + j] = (double)v;
-    }
-  }
+  int bad = load_lower<true>(jtj + (long long)b * dd, d, A, LD);
   double rk = 0.0;                                // thread k < d keeps rhs_k
   if (tid < d) {
     rk = rhs[ob + tid];
@@ -101,22 +69,7 @@ __global__ __launch_bounds__(NT) void metric_solve_kernel(const float* __restric
     }
   } else {
     // 2. pivots and multipliers; row d is rhs
-    const int ti = tid >> 4, tj = tid & 15;
-    int fail = 0;
-    for (int k = 0; k < d; ++k) {
-      const double piv = A[k * LD + k];           // uniform
-      if (!(piv > 0.0) || !(piv < 1.0e300)) {
-        fail = 1;
-        break;
-      }
-      for (int i = k + 1 + ti; i <= d; i += 16) {
-        const double aik = A[i * LD + k] / piv;    // a division: x / x = 1, a duplicate column cancels its pivot exactly
-        const int jmax = i < d ? i : d - 1;
-        for (int j = k + 1 + tj; j <= jmax; j += 16) A[i * LD + j] -= aik * A[j * LD + k];
-      }
-      __syncthreads();
-    }
-    if (fail) {                                   // uniform
+    if (eliminate(A, LD, d, d, d, 1)) {           // uniform
       if (tid < d) {
         out64[ob + tid] = nan;
         out32[ob + tid] = (float)nan;
@@ -126,13 +79,7 @@ __global__ __launch_bounds__(NT) void metric_solve_kernel(const float* __restric
       return;
     }
     // the back substitution on row d
-    double* w = A + d * LD;
-    for (int i = d - 1; i >= 0; --i) {
-      const double di = w[i] / A[i * LD + i];
-      if (tid < i) w[tid] -= A[i * LD + tid] * di;
-      if (tid == i) xs[i] = di;
-      __syncthreads();
-    }
+    back_substitute(A, LD, d, A + d * LD, xs);
     if (tid < d) ok = xs[tid];
   }
 

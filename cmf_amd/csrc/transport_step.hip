@@ -18,9 +18,8 @@
 //      division, A_ij -= (A_ik / piv) A_kj; two barriers per column.  Column k is never swapped: the pivots live in pv[].  Then the
 //      back substitution, last column first, one barrier per column; b goes straight to `bwd`.
 //   3. G_{i+1}'s lower triangle -> A with row stride d | 1, the m right-hand sides C_i^T w_i (r ascending, straight from the float32
-//      block) as rows d .. d + m - 1; the elimination of shoot_step.hip / gn_step.hip, restated here so that those kernels keep
-//      their bits, one barrier per column: the extra rows take part like any other row, which IS the forward substitution.  Then the
-//      back substitution on those rows; a goes straight to `fwd`.
+//      block) as rows d .. d + m - 1; the elimination of shoot_step.hip / gn_step.hip (dense_f64.h, eliminate) with m extra rows,
+//      which end forward-substituted.  Then the back substitution on those rows; a goes straight to `fwd`.
 //   4. out_{i+1} = 0.5 (a + b).
 // The order of every sum is a function of (d, m) alone.
 //
@@ -28,13 +27,13 @@
 // of that segment and of the later ones, out / norm2 from point i + 1 on = NaN; everything before keeps its bits); 2 a non-finite
 // value in w0 or in a part of jtj / cross that is read (every output NaN; found by a pass over the curve's inputs before anything
 // is written, so it takes precedence).
-#include "common.h"
-
 #pragma clang fp contract(off)
+#include "dense_f64.h"                             // after the pragma: the helpers are compiled without contraction
 
 namespace {
 
 constexpr int NT = 256;
+static_assert(NT == F64_NT, "dense_f64.h is written for this workgroup size");
 constexpr int MAXD = 128;
 constexpr int MAXM = 16;
 
@@ -43,17 +42,6 @@ inline __host__ __device__ int stride_chol(int d) { return d | 1; }
 inline __host__ __device__ int window(int d, int m) {
   const int a = d * stride_lu(d, m), b = (d + m) * stride_chol(d);
   return a > b ? a : b;
-}
-
-__device__ __forceinline__ bool not_finite(float v) { return !(fabsf(v) <= __FLT_MAX__); }
-__device__ __forceinline__ bool not_finite(double v) { return !(fabs(v) <= __DBL_MAX__); }
-
-// the float64 copy of a lower triangle
-__device__ __forceinline__ void load_lower(const float* __restrict__ G, int d, double* A, int LD) {
-  for (int e = threadIdx.x; e < d * d; e += NT) {
-    const int i = e / d, j = e - i * d;
-    if (j <= i) A[i * LD + j] = (double)G[e];
-  }
 }
 
 __device__ __forceinline__ void fill(double* p, long long n, double v) {
@@ -104,7 +92,7 @@ __global__ __launch_bounds__(NT) void transport_chain_kernel(const float* __rest
   for (int i = 0; i < P; ++i) {
     const double* w = o + (long long)i * md;      // [m][d], written by this workgroup before the last barrier
     // 1. u = G_i w_i into columns d .. d + m - 1; norm2_i
-    load_lower(Gc + (long long)i * dd, d, A, LB);
+    load_lower<false>(Gc + (long long)i * dd, d, A, LB);
     __syncthreads();
     for (int e = tid; e < md; e += NT) {
       const int r = e / m, c = e - r * m;
@@ -188,7 +176,7 @@ __global__ __launch_bounds__(NT) void transport_chain_kernel(const float* __rest
     }
 
     // 3. a = G_{i+1}^-1 (C_i^T w_i): pivots and multipliers on the lower triangle; rows d .. d + m - 1 are the right-hand sides
-    load_lower(Gc + (long long)(i + 1) * dd, d, A, LF);
+    load_lower<false>(Gc + (long long)(i + 1) * dd, d, A, LF);
     for (int e = tid; e < md; e += NT) {
       const int c = e / d, j = e - c * d;
       const double* wc = w + c * d;
@@ -197,20 +185,7 @@ __global__ __launch_bounds__(NT) void transport_chain_kernel(const float* __rest
       A[(d + c) * LF + j] = s;
     }
     __syncthreads();
-    for (int k = 0; k < d; ++k) {
-      const double piv = A[k * LF + k];           // uniform
-      if (!(piv > 0.0) || !(piv < 1.0e300)) {
-        fail = 1;
-        break;
-      }
-      for (int r = k + 1 + ti; r < W; r += 16) {
-        const double ark = A[r * LF + k] / piv;    // a division: x / x = 1, a duplicate column cancels its pivot exactly
-        const int jmax = r < d ? r : d - 1;
-        for (int j = k + 1 + tj; j <= jmax; j += 16) A[r * LF + j] -= ark * A[j * LF + k];
-      }
-      __syncthreads();
-    }
-    if (fail) {                                   // uniform
+    if (eliminate(A, LF, d, d, d, m)) {           // uniform
       fail_at = i;
       break;
     }
