@@ -818,7 +818,9 @@ def hutchinson_surrogate(sd, ops, z_low, eps, solve="exact"):
 def cg_documented(jtj, eps, max_iter, tol, min_iter=None):
     """The build's own CG stopping rule (cmf_amd/csrc/hutch_cg.hip), restated for checking the kernel:
     x0 = 0, unit-normalised right-hand sides, stop a sample after iteration k >= min_iter once the mean over its
-    probes of the relative residual norm is < tol; at most max_iter.  (gpytorch's linear_cg @ fc2053b, which the
+    probes of the relative residual norm is < tol; at most max_iter.  This is the rule for S <= 16 only: the kernels split
+    more probes into work items of 16 with a mean and an iteration count each (tests/_hutch_cg_reference.py models that; it
+    also guards the zero probe and p^T q = 0, which divide by zero here).  (gpytorch's linear_cg @ fc2053b, which the
     reference calls at non_square.py:241-247, is un-vendored: parity unpinned.)"""
     B, d, S = eps.shape
     if min_iter is None:
