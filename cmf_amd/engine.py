@@ -172,6 +172,16 @@ class timing:
         return False
 
 
+def _timed(name, cost, launch):
+    """Run ``launch`` under the calling thread's timer, if it has one, as an entry of the family ``name``; ``cost()`` gives the
+    launch's (flops, bytes) and is evaluated only then (it may read arguments the untimed path never touches).  ``name`` None: a
+    launch that carries no timer entry."""
+    timer = _timer()
+    if timer is None or name is None:
+        return launch()
+    return timer.wrap(name, *cost(), launch)
+
+
 def _use_bf16x3(taps, cin, W, transpose, H=None, cout=64):
     return cfg().tangent == "bf16x3" and _shape_ok_bf16x3(taps, cin, W, transpose, H, cout)
 
@@ -470,18 +480,18 @@ def conv_tangent(x_t, x_off, x_np, x_ci, x_px, weight, taps, y_t, y_np, y_co, y_
         def launch():                                       # traced: a primal launch of a tangent kernel (bench.py's stages)
             with _lib.role("primal"):
                 run()
-    TIMER = _timer()
-    if TIMER is None:
-        return launch()
-    # algorithmic work of this launch: 2*cin*cout*taps FLOP per output pixel and Jacobian column; every input,
-    # output and residual element crosses HBM once (4 bytes each)
-    px_in = float(H) * W * nc * np_
-    px = px_in * (0.5 if live else 1.0)                     # checkerboard output: half the output pixels (and residual reads), every input pixel
-    # seeded residual: + the seed K-step's 9 taps of one channel, + the panel's bytes instead of a residual's
-    TIMER.wrap(f"conv_tangent_t{taps}_ci{cin}_co{cout}" + ("_primal" if fmode == F_SELF_RELU else "_primal_bwd" if pbwd else "_live" if live else ""),
-               2.0 * (cin + (1 if seed is not None else 0)) * cout * taps * px,
-               4.0 * (px_in * cin + px * (cout + (cout if res_t is not None else 0))
-                      + (float(seed["np"]) * np_ if seed is not None else 0.0)), launch)
+
+    def cost():
+        # algorithmic work of this launch: 2*cin*cout*taps FLOP per output pixel and Jacobian column; every input,
+        # output and residual element crosses HBM once (4 bytes each)
+        px_in = float(H) * W * nc * np_
+        px = px_in * (0.5 if live else 1.0)                 # checkerboard output: half the output pixels (and residual reads), every input pixel
+        # seeded residual: + the seed K-step's 9 taps of one channel, + the panel's bytes instead of a residual's
+        return (2.0 * (cin + (1 if seed is not None else 0)) * cout * taps * px,
+                4.0 * (px_in * cin + px * (cout + (cout if res_t is not None else 0))
+                       + (float(seed["np"]) * np_ if seed is not None else 0.0)))
+    return _timed(f"conv_tangent_t{taps}_ci{cin}_co{cout}" + ("_primal" if fmode == F_SELF_RELU else "_primal_bwd" if pbwd else "_live" if live else ""),
+                  cost, launch)
 
 
 def _conv_tangent_head(lib, a, x_t, x_off, x_np, x_ci, x_px, weight, taps, y_t, y_np, y_co, y_px, np_, cin, cout, H, W, nc, fmode, f,
@@ -506,21 +516,19 @@ def _conv_tangent_head(lib, a, x_t, x_off, x_np, x_ci, x_px, weight, taps, y_t, 
     a.head_a = _p(act); a.head_a_np, a.head_a_c, a.head_a_px = int(cin) * H * W, H * W, 1
     a.head_y = C.c_void_p(y_t.data_ptr() + 4 * int(y_off)); a.head_y_np, a.head_y_co, a.head_y_px = int(y_np), int(y_co), int(y_px)
     launch = lambda: _lib.check(lib.cmf_conv_tangent_bf16x3(C.byref(a), _stream()), "cmf_conv_tangent_bf16x3")
-    TIMER = _timer()
-    if TIMER is None:
-        return launch()
-    # what the launch executes: per output pixel hc * 64 * 576 FMAs for E, then hc * 640 per column; u crosses HBM once (counted
-    # whole: the live fraction is data), h at the output pixels, the activation and yt
-    px_out = float(H) * W * np_ * (0.5 if live else 1.0)
-    if blk is not None:
-        # folded block: + the coefficient build (9 hc rows x 64 x 576 per output pixel, three bf16 products each), the apply's hc *
-        # 1600 FMAs per column; h crosses HBM once, the two bit masks, the activation and yt
-        return TIMER.wrap(f"conv_tangent_t{taps}_ci{cin}_co{cout}" + ("_live" if live else ""),
-                          2.0 * hc * px_out * (cin * taps * cout + 3 * taps * cin * taps * cout + 25 * cout * nc),
-                          4.0 * (float(H) * W * np_ * (nc * cin + 4) + px_out * (cout + nc * hc)), launch)
-    TIMER.wrap(f"conv_tangent_t{taps}_ci{cin}_co{cout}" + ("_live" if live else ""),
-               2.0 * hc * px_out * (cin * taps * cout + (cin * taps + cout) * nc),
-               4.0 * (float(H) * W * np_ * nc * cin + px_out * (nc * cout + cout + nc * hc)), launch)
+
+    def cost():
+        # what the launch executes: per output pixel hc * 64 * 576 FMAs for E, then hc * 640 per column; u crosses HBM once (counted
+        # whole: the live fraction is data), h at the output pixels, the activation and yt
+        px_out = float(H) * W * np_ * (0.5 if live else 1.0)
+        if blk is not None:
+            # folded block: + the coefficient build (9 hc rows x 64 x 576 per output pixel, three bf16 products each), the apply's hc *
+            # 1600 FMAs per column; h crosses HBM once, the two bit masks, the activation and yt
+            return (2.0 * hc * px_out * (cin * taps * cout + 3 * taps * cin * taps * cout + 25 * cout * nc),
+                    4.0 * (float(H) * W * np_ * (nc * cin + 4) + px_out * (cout + nc * hc)))
+        return (2.0 * hc * px_out * (cin * taps * cout + (cin * taps + cout) * nc),
+                4.0 * (float(H) * W * np_ * nc * cin + px_out * (nc * cout + cout + nc * hc)))
+    return _timed(f"conv_tangent_t{taps}_ci{cin}_co{cout}" + ("_live" if live else ""), cost, launch)
 
 
 _WGRAD_WS = {}
@@ -555,12 +563,11 @@ def conv_tangent_wgrad(x_t, x_off, x_np, x_ci, x_px, gy_t, gy_off, y_np, y_co, y
     fn, what = (lib.cmf_conv_tangent_wgrad_bf16x3, "cmf_conv_tangent_wgrad_bf16x3") if split else \
                (lib.cmf_conv_tangent_wgrad, "cmf_conv_tangent_wgrad")
     launch = lambda: _lib.check(fn(C.byref(a), gy, _p(dw), _p(ws), need, _stream()), what)
-    TIMER = _timer()
-    if TIMER is None:
-        return launch()
-    px = float(H) * W * nc * np_
-    TIMER.wrap(f"conv_wgrad_t{taps}_ci{cin}_co{cout}" + ("_primal" if fmode == F_SELF_RELU else ""), 2.0 * cin * cout * taps * px,
-               4.0 * px * (cin + cout), launch)
+
+    def cost():
+        px = float(H) * W * nc * np_
+        return 2.0 * cin * cout * taps * px, 4.0 * px * (cin + cout)
+    return _timed(f"conv_wgrad_t{taps}_ci{cin}_co{cout}" + ("_primal" if fmode == F_SELF_RELU else ""), cost, launch)
 
 
 def conv_tangent_wgrad_batched(xs, gys, dws, x_np, x_ci, x_px, y_np, y_co, y_px, np_, cin, cout, H, W, nc, fmode=F_NONE, x_sl=16, y_sl=16):
@@ -588,12 +595,11 @@ def conv_tangent_wgrad_batched(xs, gys, dws, x_np, x_ci, x_px, y_np, y_co, y_px,
         assert dw.dtype == torch.float32 and dw.is_contiguous() and dw.numel() == cout * cin * 9
     launch = lambda: _lib.check(lib.cmf_conv_tangent_wgrad_bf16x3_batched(C.byref(a), n, arr(xs), arr(gys), arr(dws), _p(ws), need, _stream()),
                                 "cmf_conv_tangent_wgrad_bf16x3_batched")
-    TIMER = _timer()
-    if TIMER is None:
-        return launch()
-    px = float(H) * W * nc * np_ * n
-    TIMER.wrap(f"conv_wgrad_t9_ci{cin}_co{cout}" + ("_primal" if fmode == F_SELF_RELU else "") + "_batched", 2.0 * cin * cout * 9 * px,
-               4.0 * px * (cin + cout), launch)
+
+    def cost():
+        px = float(H) * W * nc * np_ * n
+        return 2.0 * cin * cout * 9 * px, 4.0 * px * (cin + cout)
+    return _timed(f"conv_wgrad_t9_ci{cin}_co{cout}" + ("_primal" if fmode == F_SELF_RELU else "") + "_batched", cost, launch)
 
 
 def primal_regroup(t, to_grouped):
@@ -673,12 +679,12 @@ def acl_tangent(T, YT, z, y, g, maps):
     launch = lambda: _lib.check(_lib.load().cmf_acl_tangent(_p(T.data), T.t_b, T.t_r, *_t3(YT), T.nc, _p(z2),
                                                             z2.shape[1], _p(y2), y_b, _p(g), _p(maps["zi"]), _p(maps["si"]),
                                                             _p(maps["ti"]), maps["n"], B, _stream()), "cmf_acl_tangent")
-    TIMER = _timer()
-    if TIMER is None:
-        return launch()
-    # coupling pass, per modified element: tangent rows v, s-dot, t-dot in (3 x NC floats), one row out, 5 scalars
-    n = float(maps["n"]) * B
-    TIMER.wrap("acl_tangent", 4.0 * n * T.nc, 4.0 * n * ((4 if YT is not None else 2) * T.nc + 5), launch)
+
+    def cost():
+        # coupling pass, per modified element: tangent rows v, s-dot, t-dot in (3 x NC floats), one row out, 5 scalars
+        n = float(maps["n"]) * B
+        return 4.0 * n * T.nc, 4.0 * n * ((4 if YT is not None else 2) * T.nc + 5)
+    return _timed("acl_tangent", cost, launch)
 
 
 def acl_cotangent(Ct, YC, z, y, g, maps):
@@ -809,15 +815,15 @@ def gram_cholesky(T, d, max_attempts=6, eps0=1e-6):
     launch = lambda: _lib.check(lib.cmf_gram_cholesky(_p(T.data), T.t_b, T.t_r, T.N, T.nc, d, T.B, _p(r.jtj), _p(r.logdet),
                                                       _p(r.l1_off), _p(r.l1_diag), _p(r.info), _p(r.fail), _stream()),
                                 "cmf_gram_cholesky")
-    TIMER = _timer()
-    if TIMER is None:
-        launch()
-    elif T.nc <= WIDE_NC:                          # 2 D d^2 (+ d^3/3) FLOP and (D NC + d^2 + 3) 4 B per sample
-        TIMER.wrap("gram_cholesky", T.B * (2.0 * T.N * d * d + d ** 3 / 3.0), 4.0 * T.B * (T.N * T.nc + d * d + 3), launch)
-    else:                                          # head_wide.hip: the lower-triangle tiles (half the products) and the
-        nt = -(-d // 64)                           # factorisation's passes over jtj (l1 sums, panels, trailing updates, restore)
-        TIMER.wrap("gram_cholesky_wide", T.B * (2.0 * T.N * d * d + d ** 3 / 3.0),
-                   4.0 * T.B * (nt * (nt + 1) // 2 * 2 * 64 * T.N + 4 * d * d + d ** 3 / 96.0), launch)
+
+    def cost():
+        if T.nc <= WIDE_NC:                        # 2 D d^2 (+ d^3/3) FLOP and (D NC + d^2 + 3) 4 B per sample
+            return T.B * (2.0 * T.N * d * d + d ** 3 / 3.0), 4.0 * T.B * (T.N * T.nc + d * d + 3)
+        # head_wide.hip: the lower-triangle tiles (half the products) and the factorisation's passes over jtj (l1 sums, panels,
+        # trailing updates, restore)
+        nt = -(-d // 64)
+        return T.B * (2.0 * T.N * d * d + d ** 3 / 3.0), 4.0 * T.B * (nt * (nt + 1) // 2 * 2 * 64 * T.N + 4 * d * d + d ** 3 / 96.0)
+    _timed("gram_cholesky" if T.nc <= WIDE_NC else "gram_cholesky_wide", cost, launch)
     cholesky_retries(r, d, max_attempts, eps0)
     return r
 
@@ -847,14 +853,13 @@ def gram_condition(r, d, threshold):
     launch = lambda: _lib.check(_lib.load().cmf_gram_condition(_p(r.jtj), _p(r.info), d, B, float(threshold), _p(r.cond),
                                                                _p(r.flagged_idx), _p(r.flagged_count), _p(ws), _stream()),
                                 "cmf_gram_condition")
-    TIMER = _timer()
-    if TIMER is None:
-        launch()
-    else:
+
+    def cost():
         # float64 multiply-adds: factorisation d^3/6, triangular inverse d^3/6, |G^-1| column sums d^3/3 (2 FLOP each); bytes:
         # jtj in and cond out, plus for 128 < d the float64 matrix written once and re-read by every pass over it in L2 / HBM
         wide = 8.0 * (d * d + 2 * d ** 3 / 3.0) if d > WIDE_NC else 0.0
-        TIMER.wrap("gram_condition", B * 2.0 * (2 * d ** 3 / 3.0), B * (4.0 * (d * d + 1) + wide) + 8.0 * B, launch)
+        return B * 2.0 * (2 * d ** 3 / 3.0), B * (4.0 * (d * d + 1) + wide) + 8.0 * B
+    _timed("gram_condition", cost, launch)
     return r
 
 
@@ -904,14 +909,63 @@ def metric_stats_accumulate(jtj, state, workspace=None, sample_macs=None):
     launch = lambda: _lib.check(_lib.load().cmf_metric_stats_accumulate(
         _p(jtj), d, B, METRIC_STATS_CHUNK, _p(state), _p(workspace), workspace.numel(), _p(sample_macs), _stream()),
         "cmf_metric_stats_accumulate")
-    TIMER = _timer()
-    if TIMER is None:
-        launch()
-    else:
+
+    def cost():
         # per element one conversion, two multiplies, two adds and an abs in float64; bytes: jtj in, the chunk partials out and in
         n_chunks = -(-B // METRIC_STATS_CHUNK)
-        TIMER.wrap("metric_stats", 6.0 * B * d * d, 4.0 * B * d * d + 16.0 * (n_chunks + 1) * metric_stats_state_size(d), launch)
+        return 6.0 * B * d * d, 4.0 * B * d * d + 16.0 * (n_chunks + 1) * metric_stats_state_size(d)
+    _timed("metric_stats", cost, launch)
     return state
+
+
+# the argument rules of the head and manifold wrappers below, each stated once; all raise ValueError before any launch
+
+
+def _check_on_gpu(name, t):
+    if not isinstance(t, torch.Tensor) or not t.is_cuda:
+        raise ValueError(f"{name} must be on the GPU, got {getattr(t, 'device', type(t).__name__)} (there is no CPU fallback)")
+
+
+def _check_tensor(name, t, dtype, want=None, fits=None, device=None):
+    """``t`` is a tensor on the GPU of ``dtype`` and, with ``want`` -- the words for its shape --, contiguous, of a shape that
+    ``fits(t)`` accepts and, where one is given, on ``device``."""
+    _check_on_gpu(name, t)
+    if t.dtype != dtype:
+        raise ValueError(f"{name} must be {str(dtype).split('.')[1]}, got {t.dtype}")
+    if want is not None and not (fits(t) and t.is_contiguous() and (device is None or t.device == device)):
+        on, on_t = ("", "") if device is None else (f" on {device}", f" on {t.device}")
+        raise ValueError(f"{name} must be a contiguous {want} tensor{on}, got {tuple(t.shape)}{on_t}"
+                         f"{'' if t.is_contiguous() else ' (not contiguous)'}")
+
+
+def _check_width(d, kernel, limit):
+    if not 1 <= d <= limit:
+        raise ValueError(f"d = {d}: {kernel} 1 <= d <= {limit}")
+
+
+def _gram_stack(jtj, rows, kernel, limit):
+    """``jtj`` is a contiguous float32 (``rows``, d, d) stack on the GPU, no wider than ``kernel`` takes: returns (its rows, d)."""
+    _check_tensor("jtj", jtj, torch.float32, f"({rows}, d, d)", lambda t: t.dim() == 3 and t.shape[1] == t.shape[2])
+    _check_width(jtj.shape[1], kernel, limit)
+    return jtj.shape[0], jtj.shape[1]
+
+
+def _check_tangent(T):
+    if not isinstance(T, Tangent):
+        raise ValueError(f"T must be an engine.Tangent, got {type(T).__name__}")
+
+
+def _whole_curves(points, rows, name, least=3):
+    """The number of curves of ``points`` points in the ``rows`` curve-major samples of ``name``."""
+    if points < least or rows % points:
+        raise ValueError(f"points = {points}: a curve needs points >= {least}, and the {rows} samples of {name} must be whole curves")
+    return rows // points
+
+
+def _check_damping(damping, rows, dev):
+    if not isinstance(damping, torch.Tensor) or damping.dtype != torch.float64 or damping.device != dev or \
+            damping.shape != (rows,) or not damping.is_contiguous():
+        raise ValueError(f"damping must be {rows} contiguous float64 values on {dev}")
 
 
 #: widest Gram matrix ``gram_spectrum`` takes: the float64 matrix of a sample lives in LDS (csrc/gram_spectrum.hip)
@@ -929,16 +983,7 @@ def gram_spectrum(jtj, vectors=False):
     """Eigenvalues (and, with ``vectors``, eigenvectors) of every (d, d) matrix of ``jtj`` (B, d, d) float32, whose lower
     triangles are read: float64 cyclic Jacobi, one workgroup per sample.  Deterministic per sample; enqueues one
     launch, no synchronisation."""
-    if not isinstance(jtj, torch.Tensor) or not jtj.is_cuda:
-        raise ValueError(f"jtj must be on the GPU, got {getattr(jtj, 'device', type(jtj).__name__)} (there is no CPU fallback)")
-    if jtj.dtype != torch.float32:
-        raise ValueError(f"jtj must be float32, got {jtj.dtype}")
-    if jtj.dim() != 3 or jtj.shape[1] != jtj.shape[2] or not jtj.is_contiguous():
-        raise ValueError(f"jtj must be a contiguous (B, d, d) tensor, got {tuple(jtj.shape)}"
-                         f"{'' if jtj.is_contiguous() else ' (not contiguous)'}")
-    B, d = jtj.shape[0], jtj.shape[1]
-    if not 1 <= d <= SPECTRUM_MAX_WIDTH:
-        raise ValueError(f"d = {d}: the spectrum kernel supports 1 <= d <= {SPECTRUM_MAX_WIDTH}")
+    B, d = _gram_stack(jtj, "B", "the spectrum kernel supports", SPECTRUM_MAX_WIDTH)
     r = SpectrumResult()
     r.eigenvalues = torch.empty(B, d, dtype=torch.float64, device=jtj.device)
     r.vectors = torch.empty(B, d, d, dtype=torch.float64, device=jtj.device) if vectors else None
@@ -948,14 +993,10 @@ def gram_spectrum(jtj, vectors=False):
         return r
     launch = lambda: _lib.check(_lib.load().cmf_gram_spectrum(_p(jtj), d, B, _p(r.eigenvalues), _p(r.vectors), _p(r.sweeps),
                                                               _p(r.info), _stream()), "cmf_gram_spectrum")
-    TIMER = _timer()
-    if TIMER is None:
-        launch()
-    else:
-        # a nominal 10 sweeps of d (d - 1) / 2 rotations, each 6 float64 FLOP on 2 d entry pairs of A (+ d of V); bytes: jtj in,
-        # the outputs out (the iteration itself runs in LDS)
-        TIMER.wrap("gram_spectrum", B * 10.0 * (d * (d - 1) / 2) * 6.0 * (3 if vectors else 2) * d,
-                   B * (4.0 * d * d + 8.0 * d + (8.0 * d * d if vectors else 0.0) + 8.0), launch)
+    # a nominal 10 sweeps of d (d - 1) / 2 rotations, each 6 float64 FLOP on 2 d entry pairs of A (+ d of V); bytes: jtj in,
+    # the outputs out (the iteration itself runs in LDS)
+    _timed("gram_spectrum", lambda: (B * 10.0 * (d * (d - 1) / 2) * 6.0 * (3 if vectors else 2) * d,
+                                     B * (4.0 * d * d + 8.0 * d + (8.0 * d * d if vectors else 0.0) + 8.0)), launch)
     return r
 
 
@@ -973,13 +1014,7 @@ class GaussNewtonResult:
 def _residual_pair(x, xhat):
     """The checks ``gauss_newton_step`` and ``residual_sqnorm`` share; returns (B, elements per sample)."""
     for name, v in (("x", x), ("xhat", xhat)):
-        if not isinstance(v, torch.Tensor) or not v.is_cuda:
-            raise ValueError(f"{name} must be on the GPU, got {getattr(v, 'device', type(v).__name__)} (there is no CPU fallback)")
-        if v.dtype != torch.float32:
-            raise ValueError(f"{name} must be float32, got {v.dtype}")
-        if v.dim() < 2 or not v.is_contiguous():
-            raise ValueError(f"{name} must be a contiguous (B, ...) tensor, got {tuple(v.shape)}"
-                             f"{'' if v.is_contiguous() else ' (not contiguous)'}")
+        _check_tensor(name, v, torch.float32, "(B, ...)", lambda t: t.dim() >= 2)
     if x.shape != xhat.shape or x.device != xhat.device:
         raise ValueError(f"x {tuple(x.shape)} on {x.device} and xhat {tuple(xhat.shape)} on {xhat.device} must agree")
     B = x.shape[0]
@@ -1000,11 +1035,8 @@ def residual_sqnorm(x, xhat):
         return stats[:, 0], info
     launch = lambda: _lib.check(_lib.load().cmf_gauss_newton_step(None, 0, 0, n, 0, 0, B, None, _p(x), _p(xhat), None, None, None,
                                                                   _p(stats), _p(info), _stream()), "cmf_gauss_newton_step")
-    TIMER = _timer()
-    if TIMER is None:
-        launch()
-    else:                                          # a subtraction, a multiply and an add per element; x and xhat in
-        TIMER.wrap("residual_sqnorm", 3.0 * B * n, B * (8.0 * n + 12.0), launch)
+    # a subtraction, a multiply and an add per element; x and xhat in
+    _timed("residual_sqnorm", lambda: (3.0 * B * n, B * (8.0 * n + 12.0)), launch)
     return stats[:, 0], info
 
 
@@ -1013,26 +1045,14 @@ def gauss_newton_step(T, jtj, x, xhat, damping):
     ``jtj`` (B, d, d) float32 (one ``gram_cholesky`` attempt; the lower triangles are read), the head-space input ``x`` and the
     reconstruction ``xhat`` (B, ...) float32 and ``damping`` (B,) float64 >= 0, in float64: grad = J^T (x - xhat) and delta =
     (G + damping diag G)^-1 grad.  Returns a ``GaussNewtonResult``.  Deterministic per sample; one launch, no synchronisation."""
-    if not isinstance(T, Tangent):
-        raise ValueError(f"T must be an engine.Tangent, got {type(T).__name__}")
+    _check_tangent(T)
     B, n = _residual_pair(x, xhat)
     dev = x.device
-    if not isinstance(jtj, torch.Tensor) or not jtj.is_cuda:
-        raise ValueError(f"jtj must be on the GPU, got {getattr(jtj, 'device', type(jtj).__name__)} (there is no CPU fallback)")
-    if jtj.dtype != torch.float32:
-        raise ValueError(f"jtj must be float32, got {jtj.dtype}")
-    if jtj.dim() != 3 or jtj.shape[1] != jtj.shape[2] or not jtj.is_contiguous():
-        raise ValueError(f"jtj must be a contiguous (B, d, d) tensor, got {tuple(jtj.shape)}"
-                         f"{'' if jtj.is_contiguous() else ' (not contiguous)'}")
-    d = jtj.shape[1]
-    if not 1 <= d <= PROJECT_MAX_WIDTH:
-        raise ValueError(f"d = {d}: the Gauss-Newton step kernel supports 1 <= d <= {PROJECT_MAX_WIDTH}")
+    _, d = _gram_stack(jtj, "B", "the Gauss-Newton step kernel supports", PROJECT_MAX_WIDTH)
     if T.B != B or T.N != n or T.nc % 16 or T.nc < d or jtj.shape[0] != B or T.data.device != dev or jtj.device != dev:
         raise ValueError(f"T (B = {T.B}, N = {T.N}, nc = {T.nc}) on {T.data.device} must hold d = {d} <= nc columns, nc % 16 == 0, "
                          f"for the {B} samples of {n} elements of x on {dev}, like jtj {tuple(jtj.shape)} on {jtj.device}")
-    if not isinstance(damping, torch.Tensor) or damping.dtype != torch.float64 or damping.device != dev or \
-            damping.shape != (B,) or not damping.is_contiguous():
-        raise ValueError(f"damping must be {B} contiguous float64 values on {dev}")
+    _check_damping(damping, B, dev)
     r = GaussNewtonResult()
     r.grad = torch.empty(B, d, dtype=torch.float64, device=dev)
     r.delta = torch.empty(B, d, dtype=torch.float64, device=dev)
@@ -1043,15 +1063,14 @@ def gauss_newton_step(T, jtj, x, xhat, damping):
     launch = lambda: _lib.check(_lib.load().cmf_gauss_newton_step(_p(T.data), T.t_b, T.t_r, n, T.nc, d, B, _p(jtj), _p(x), _p(xhat),
                                                                   _p(damping), _p(r.grad), _p(r.delta), _p(r.stats), _p(r.info),
                                                                   _stream()), "cmf_gauss_newton_step")
-    TIMER = _timer()
-    if TIMER is None:
-        launch()
-    else:
+
+    def cost():
         # float64: J^T r 2 D d, the elimination d^3 / 3 with the two substitutions 2 d^2, the residual 3 D and the two forms
         # 3 d^2 / 2 + 2 d; bytes: the live quarter-rows of J, x and xhat twice (L2 the second time), the triangle of G twice, the outputs
         ncl = min(T.nc, -(-d // 4) * 4)
-        TIMER.wrap("gauss_newton_step", B * (2.0 * n * d + d ** 3 / 3.0 + 3.5 * d * d + 3.0 * n + 2.0 * d),
-                   B * (4.0 * n * ncl + 16.0 * n + 4.0 * d * (d + 1) + 16.0 * d + 44.0), launch)
+        return (B * (2.0 * n * d + d ** 3 / 3.0 + 3.5 * d * d + 3.0 * n + 2.0 * d),
+                B * (4.0 * n * ncl + 16.0 * n + 4.0 * d * (d + 1) + 16.0 * d + 44.0))
+    _timed("gauss_newton_step", cost, launch)
     return r
 
 
@@ -1070,31 +1089,19 @@ class CurveStepResult:
 
 def _curve_points(xhat, points):
     """The checks ``curve_step`` and ``curve_energy`` share; returns (curves, elements per point)."""
-    if not isinstance(xhat, torch.Tensor) or not xhat.is_cuda:
-        raise ValueError(f"xhat must be on the GPU, got {getattr(xhat, 'device', type(xhat).__name__)} (there is no CPU fallback)")
-    if xhat.dtype != torch.float32:
-        raise ValueError(f"xhat must be float32, got {xhat.dtype}")
-    if xhat.dim() < 2 or not xhat.is_contiguous():
-        raise ValueError(f"xhat must be a contiguous (curves * points, ...) tensor, got {tuple(xhat.shape)}"
-                         f"{'' if xhat.is_contiguous() else ' (not contiguous)'}")
-    points = int(points)
-    if points < 3 or xhat.shape[0] % points:
-        raise ValueError(f"points = {points}: a curve needs points >= 3, and the {xhat.shape[0]} samples of xhat must be whole curves")
+    _check_tensor("xhat", xhat, torch.float32, "(curves * points, ...)", lambda t: t.dim() >= 2)
+    curves = _whole_curves(int(points), xhat.shape[0], "xhat")
     n = int(np.prod(xhat.shape[1:]))
     if n < 1:
         raise ValueError(f"xhat must have at least one element per point, got {tuple(xhat.shape)}")
-    return xhat.shape[0] // points, n
+    return curves, n
 
 
 def _curve_tangent(T, d, points):
-    if not isinstance(T, Tangent):
-        raise ValueError(f"T must be an engine.Tangent, got {type(T).__name__}")
-    if not T.data.is_cuda:
-        raise ValueError(f"T must be on the GPU, got {T.data.device} (there is no CPU fallback)")
-    if not 1 <= int(d) <= GEODESIC_MAX_WIDTH:
-        raise ValueError(f"d = {int(d)}: the curve kernels support 1 <= d <= {GEODESIC_MAX_WIDTH}")
-    if int(points) < 3 or T.B % int(points):
-        raise ValueError(f"points = {int(points)}: a curve needs points >= 3, and the {T.B} samples of T must be whole curves")
+    _check_tangent(T)
+    _check_on_gpu("T", T.data)
+    _check_width(int(d), "the curve kernels support", GEODESIC_MAX_WIDTH)
+    _whole_curves(int(points), T.B, "T")
     if T.nc % 16 or T.nc < d or T.nc > GEODESIC_MAX_WIDTH:
         raise ValueError(f"T (nc = {T.nc}) must hold d = {int(d)} <= nc <= {GEODESIC_MAX_WIDTH} columns, nc % 16 == 0")
 
@@ -1111,12 +1118,11 @@ def cross_gram(T, d, points):
         return out
     launch = lambda: _lib.check(_lib.load().cmf_cross_gram(_p(T.data), T.t_b, T.t_r, T.N, T.nc, d, points, curves, _p(out), _stream()),
                                 "cmf_cross_gram")
-    TIMER = _timer()
-    if TIMER is None:
-        launch()
-    else:                                          # 2 D d^2 FLOP per pair; both panels in, the block out
+
+    def cost():                                    # 2 D d^2 FLOP per pair; both panels in, the block out
         pairs = curves * (points - 3)
-        TIMER.wrap("cross_gram", pairs * 2.0 * T.N * d * d, 4.0 * pairs * (2 * T.N * T.nc + d * d), launch)
+        return pairs * 2.0 * T.N * d * d, 4.0 * pairs * (2 * T.N * T.nc + d * d)
+    _timed("cross_gram", cost, launch)
     return out
 
 
@@ -1134,11 +1140,8 @@ def curve_energy(xhat, points):
         return seg2, stats[:, 0], info
     launch = lambda: _lib.check(_lib.load().cmf_curve_step(None, 0, 0, n, 0, 0, points, curves, None, None, _p(xhat), None, None, None,
                                                            _p(stats), _p(seg2), _p(info), None, 0, _stream()), "cmf_curve_step")
-    TIMER = _timer()
-    if TIMER is None:
-        launch()
-    else:                                          # a subtraction, a multiply and an add per element and segment; xhat in twice
-        TIMER.wrap("curve_energy", 3.0 * curves * (points - 1) * n, curves * (8.0 * (points - 1) * n + 8.0 * points + 4.0), launch)
+    # a subtraction, a multiply and an add per element and segment; xhat in twice
+    _timed("curve_energy", lambda: (3.0 * curves * (points - 1) * n, curves * (8.0 * (points - 1) * n + 8.0 * points + 4.0)), launch)
     return seg2, stats[:, 0], info
 
 
@@ -1151,26 +1154,14 @@ def curve_step(T, jtj, cross, xhat, points, damping):
     synchronisation."""
     curves, n = _curve_points(xhat, points)
     points, dev = int(points), xhat.device
-    for name, v in (("jtj", jtj), ("cross", cross)):
-        if not isinstance(v, torch.Tensor) or not v.is_cuda:
-            raise ValueError(f"{name} must be on the GPU, got {getattr(v, 'device', type(v).__name__)} (there is no CPU fallback)")
-        if v.dtype != torch.float32:
-            raise ValueError(f"{name} must be float32, got {v.dtype}")
-    if jtj.dim() != 3 or jtj.shape[1] != jtj.shape[2] or not jtj.is_contiguous():
-        raise ValueError(f"jtj must be a contiguous (curves * points, d, d) tensor, got {tuple(jtj.shape)}"
-                         f"{'' if jtj.is_contiguous() else ' (not contiguous)'}")
-    d = jtj.shape[1]
+    _, d = _gram_stack(jtj, "curves * points", "the curve kernels support", GEODESIC_MAX_WIDTH)
     _curve_tangent(T, d, points)
-    if cross.shape != (curves, points - 3, d, d) or not cross.is_contiguous():
-        raise ValueError(f"cross must be a contiguous ({curves}, {points - 3}, {d}, {d}) tensor, got {tuple(cross.shape)}"
-                         f"{'' if cross.is_contiguous() else ' (not contiguous)'}")
+    _check_tensor("cross", cross, torch.float32, f"({curves}, {points - 3}, {d}, {d})", lambda t: t.shape == (curves, points - 3, d, d))
     if T.B != curves * points or T.N != n or jtj.shape[0] != T.B or T.data.device != dev or jtj.device != dev or cross.device != dev:
         raise ValueError(f"T (B = {T.B}, N = {T.N}, nc = {T.nc}) on {T.data.device} must hold d = {d} <= nc columns, nc % 16 == 0, "
                          f"for the {curves * points} samples of {n} elements of xhat on {dev}, like jtj {tuple(jtj.shape)} on "
                          f"{jtj.device} and cross on {cross.device}")
-    if not isinstance(damping, torch.Tensor) or damping.dtype != torch.float64 or damping.device != dev or \
-            damping.shape != (curves,) or not damping.is_contiguous():
-        raise ValueError(f"damping must be {curves} contiguous float64 values on {dev}")
+    _check_damping(damping, curves, dev)
     r = CurveStepResult()
     r.grad = torch.empty(curves, points - 2, d, dtype=torch.float64, device=dev)
     r.delta = torch.empty(curves, points - 2, d, dtype=torch.float64, device=dev)
@@ -1186,17 +1177,16 @@ def curve_step(T, jtj, cross, xhat, points, damping):
     launch = lambda: _lib.check(lib.cmf_curve_step(_p(T.data), T.t_b, T.t_r, n, T.nc, d, points, curves, _p(jtj),
                                                    _p(cross) if cross.numel() else None, _p(xhat), _p(damping), _p(r.grad), _p(r.delta),
                                                    _p(r.stats), _p(r.seg2), _p(r.info), _p(ws), need, _stream()), "cmf_curve_step")
-    TIMER = _timer()
-    if TIMER is None:
-        launch()
-    else:
+
+    def cost():
         # float64 per curve: J^T s 2 D d per interior point, the block elimination 7 d^3 / 3 per block (d columns on a 2 d window)
         # with the substitutions 6 d^2, the segments 3 D, the forms 5 d^2; bytes: the live quarter-rows of J, three rows of xhat per
         # point, jtj and cross three times, the eliminated columns out and in, the outputs
         M, ncl = points - 2, min(T.nc, -(-d // 4) * 4)
-        TIMER.wrap("curve_step", curves * (M * (2.0 * n * d + 7.0 * d ** 3 / 3.0 + 11.0 * d * d) + 3.0 * (points - 1) * n),
-                   curves * (M * (4.0 * n * ncl + 12.0 * n + 20.0 * d * d + 16.0 * (2 * d + 1) * d + 16.0 * d)
-                             + 8.0 * points * n + 8.0 * points + 36.0), launch)
+        return (curves * (M * (2.0 * n * d + 7.0 * d ** 3 / 3.0 + 11.0 * d * d) + 3.0 * (points - 1) * n),
+                curves * (M * (4.0 * n * ncl + 12.0 * n + 20.0 * d * d + 16.0 * (2 * d + 1) * d + 16.0 * d)
+                          + 8.0 * points * n + 8.0 * points + 36.0))
+    _timed("curve_step", cost, launch)
     return r
 
 
@@ -1217,23 +1207,9 @@ def metric_solve(jtj, rhs, apply=False):
     momentum, ``stats[:, 0]`` the squared speed -- or, with ``apply``, out = G rhs -- the momentum of a velocity.  Returns a
     ``MetricSolveResult``; ``out32[:, :, None]`` is the ``eps`` of a one-direction sweep.  Deterministic per sample; one launch,
     no synchronisation."""
-    if not isinstance(jtj, torch.Tensor) or not jtj.is_cuda:
-        raise ValueError(f"jtj must be on the GPU, got {getattr(jtj, 'device', type(jtj).__name__)} (there is no CPU fallback)")
-    if jtj.dtype != torch.float32:
-        raise ValueError(f"jtj must be float32, got {jtj.dtype}")
-    if jtj.dim() != 3 or jtj.shape[1] != jtj.shape[2] or not jtj.is_contiguous():
-        raise ValueError(f"jtj must be a contiguous (B, d, d) tensor, got {tuple(jtj.shape)}"
-                         f"{'' if jtj.is_contiguous() else ' (not contiguous)'}")
-    B, d, dev = jtj.shape[0], jtj.shape[1], jtj.device
-    if not 1 <= d <= SHOOT_MAX_WIDTH:
-        raise ValueError(f"d = {d}: the metric solve kernel supports 1 <= d <= {SHOOT_MAX_WIDTH}")
-    if not isinstance(rhs, torch.Tensor) or not rhs.is_cuda:
-        raise ValueError(f"rhs must be on the GPU, got {getattr(rhs, 'device', type(rhs).__name__)} (there is no CPU fallback)")
-    if rhs.dtype != torch.float64:
-        raise ValueError(f"rhs must be float64, got {rhs.dtype}")
-    if rhs.shape != (B, d) or rhs.device != dev or not rhs.is_contiguous():
-        raise ValueError(f"rhs must be a contiguous ({B}, {d}) tensor on {dev}, got {tuple(rhs.shape)} on {rhs.device}"
-                         f"{'' if rhs.is_contiguous() else ' (not contiguous)'}")
+    B, d = _gram_stack(jtj, "B", "the metric solve kernel supports", SHOOT_MAX_WIDTH)
+    dev = jtj.device
+    _check_tensor("rhs", rhs, torch.float64, f"({B}, {d})", lambda t: t.shape == (B, d), dev)
     r = MetricSolveResult()
     r.out64 = torch.empty(B, d, dtype=torch.float64, device=dev)
     r.out32 = torch.empty(B, d, dtype=torch.float32, device=dev)
@@ -1243,14 +1219,10 @@ def metric_solve(jtj, rhs, apply=False):
         return r
     launch = lambda: _lib.check(_lib.load().cmf_metric_solve(_p(jtj), _p(rhs), d, B, int(bool(apply)), _p(r.out64), _p(r.out32),
                                                              _p(r.stats), _p(r.info), _stream()), "cmf_metric_solve")
-    TIMER = _timer()
-    if TIMER is None:
-        launch()
-    else:
-        # float64: the elimination d^3 / 3 with the two substitutions 2 d^2 (apply: the product 2 d^2), the form 2 d; bytes: the
-        # triangle of G and rhs in, the outputs
-        TIMER.wrap("metric_solve", B * ((2.0 * d * d if apply else d ** 3 / 3.0 + 2.0 * d * d) + 2.0 * d),
-                   B * (2.0 * d * (d + 1) + 20.0 * d + 20.0), launch)
+    # float64: the elimination d^3 / 3 with the two substitutions 2 d^2 (apply: the product 2 d^2), the form 2 d; bytes: the
+    # triangle of G and rhs in, the outputs
+    _timed("metric_solve", lambda: (B * ((2.0 * d * d if apply else d ** 3 / 3.0 + 2.0 * d * d) + 2.0 * d),
+                                    B * (2.0 * d * (d + 1) + 20.0 * d + 20.0)), launch)
     return r
 
 
@@ -1276,30 +1248,14 @@ def transport_chain(jtj, cross, w0, points):
     are not read) and the vectors ``w0`` (curves, m, d) float64 at the first points, in float64 per segment: fwd = G_{i+1}^-1 C_i^T w,
     bwd = C_i^-1 G_i w, w <- (fwd + bwd) / 2.  Returns a ``TransportResult``.  Deterministic per curve; one launch, no
     synchronisation."""
-    for name, v in (("jtj", jtj), ("cross", cross), ("w0", w0)):
-        if not isinstance(v, torch.Tensor) or not v.is_cuda:
-            raise ValueError(f"{name} must be on the GPU, got {getattr(v, 'device', type(v).__name__)} (there is no CPU fallback)")
-        want = torch.float64 if name == "w0" else torch.float32
-        if v.dtype != want:
-            raise ValueError(f"{name} must be {str(want).split('.')[1]}, got {v.dtype}")
-    if jtj.dim() != 3 or jtj.shape[1] != jtj.shape[2] or not jtj.is_contiguous():
-        raise ValueError(f"jtj must be a contiguous (curves * points, d, d) tensor, got {tuple(jtj.shape)}"
-                         f"{'' if jtj.is_contiguous() else ' (not contiguous)'}")
-    d, dev, points = jtj.shape[1], jtj.device, int(points)
-    if not 1 <= d <= TRANSPORT_MAX_WIDTH:
-        raise ValueError(f"d = {d}: the transport kernel supports 1 <= d <= {TRANSPORT_MAX_WIDTH}")
-    if points < 2 or jtj.shape[0] % points:
-        raise ValueError(f"points = {points}: a curve needs points >= 2, and the {jtj.shape[0]} samples of jtj must be whole curves")
-    curves = jtj.shape[0] // points
-    if w0.dim() != 3 or w0.shape[0] != curves or w0.shape[2] != d or w0.device != dev or not w0.is_contiguous():
-        raise ValueError(f"w0 must be a contiguous ({curves}, m, {d}) tensor on {dev}, got {tuple(w0.shape)} on {w0.device}"
-                         f"{'' if w0.is_contiguous() else ' (not contiguous)'}")
+    rows, d = _gram_stack(jtj, "curves * points", "the transport kernel supports", TRANSPORT_MAX_WIDTH)
+    dev, points = jtj.device, int(points)
+    curves = _whole_curves(points, rows, "jtj", least=2)
+    _check_tensor("w0", w0, torch.float64, f"({curves}, m, {d})", lambda t: t.dim() == 3 and t.shape[0] == curves and t.shape[2] == d, dev)
     m = w0.shape[1]
     if not 1 <= m <= TRANSPORT_MAX_VECTORS:
         raise ValueError(f"m = {m}: the transport kernel takes 1 <= m <= {TRANSPORT_MAX_VECTORS} vectors per launch")
-    if cross.shape != (max(curves * points - 1, 0), d, d) or cross.device != dev or not cross.is_contiguous():
-        raise ValueError(f"cross must be a contiguous ({max(curves * points - 1, 0)}, {d}, {d}) tensor on {dev}, got "
-                         f"{tuple(cross.shape)} on {cross.device}{'' if cross.is_contiguous() else ' (not contiguous)'}")
+    _check_tensor("cross", cross, torch.float32, f"({max(rows - 1, 0)}, {d}, {d})", lambda t: t.shape == (max(rows - 1, 0), d, d), dev)
     r = TransportResult()
     r.out = torch.empty(curves, points, m, d, dtype=torch.float64, device=dev)
     r.fwd = torch.empty(curves, points - 1, m, d, dtype=torch.float64, device=dev)
@@ -1310,15 +1266,14 @@ def transport_chain(jtj, cross, w0, points):
         return r
     launch = lambda: _lib.check(_lib.load().cmf_transport_chain(_p(jtj), _p(cross), _p(w0), d, m, points, curves, _p(r.out), _p(r.fwd),
                                                                 _p(r.bwd), _p(r.norm2), _p(r.info), _stream()), "cmf_transport_chain")
-    TIMER = _timer()
-    if TIMER is None:
-        launch()
-    else:
+
+    def cost():
         # float64 per segment: the LU 2 d^3 / 3 and the Cholesky d^3 / 3 with their right-hand sides 3 m d^2 and the substitutions
         # 3 m d^2, the two products 4 m d^2; bytes: jtj three times (the check, the product, the triangle), cross three times, the outputs
         N = points - 1
-        TIMER.wrap("transport_chain", curves * (N * (d ** 3 + 10.0 * m * d * d) + 2.0 * points * m * d * d),
-                   curves * (12.0 * (points + N) * d * d + 8.0 * (points + 2 * N) * m * d + 8.0 * m * d + 8.0 * points * m + 4.0), launch)
+        return (curves * (N * (d ** 3 + 10.0 * m * d * d) + 2.0 * points * m * d * d),
+                curves * (12.0 * (points + N) * d * d + 8.0 * (points + 2 * N) * m * d + 8.0 * m * d + 8.0 * points * m + 4.0))
+    _timed("transport_chain", cost, launch)
     return r
 
 
@@ -1337,12 +1292,9 @@ def gram_backward(T, jtj, g_logdet=None, g_l1off=None, g_l1diag=None):
         launch = lambda: _lib.check(_lib.load().cmf_gram_backward_ws(
             _p(T.data), T.t_b, T.t_r, T.N, T.nc, d, B, _p(jtj), *[None if g is None else _p(g) for g in gs], _p(dT.data), dT.t_b,
             dT.t_r, _p(ws), _stream()), "cmf_gram_backward_ws")
-        TIMER = _timer()
-        if TIMER is None:
-            launch()
-        else:                                      # factor d^3/3, inverse ~d^3, product 2 D NC d; panel in and out, 4 d^2 of ws
-            TIMER.wrap("gram_backward_wide", B * (d ** 3 * 4 / 3.0 + 2.0 * T.N * T.nc * d),
-                       4.0 * B * (2 * T.N * T.nc + 6 * d * d), launch)
+        # factor d^3/3, inverse ~d^3, product 2 D NC d; panel in and out, 4 d^2 of ws
+        _timed("gram_backward_wide", lambda: (B * (d ** 3 * 4 / 3.0 + 2.0 * T.N * T.nc * d), 4.0 * B * (2 * T.N * T.nc + 6 * d * d)),
+               launch)
         return dT
     _lib.check(_lib.load().cmf_gram_backward(_p(T.data), T.t_b, T.t_r, T.N, T.nc, d, B, _p(jtj),
                                              *[None if g is None else _p(g) for g in gs], _p(dT.data), dT.t_b, dT.t_r,
@@ -1359,11 +1311,8 @@ def gram_backward_matrix(T, M):
     Mc = M.to(torch.float32).contiguous()
     launch = lambda: _lib.check(_lib.load().cmf_gram_backward_matrix(_p(T.data), T.t_b, T.t_r, T.N, T.nc, d, B, _p(Mc), _p(dT.data),
                                                                      dT.t_b, dT.t_r, _stream()), "cmf_gram_backward_matrix")
-    TIMER = _timer()
-    if TIMER is None or T.nc <= WIDE_NC:
-        launch()
-    else:
-        TIMER.wrap("gram_backward_matrix_wide", 2.0 * B * T.N * T.nc * d, 4.0 * B * (2 * T.N * T.nc + 2 * d * d), launch)
+    _timed("gram_backward_matrix_wide" if T.nc > WIDE_NC else None,
+           lambda: (2.0 * B * T.N * T.nc * d, 4.0 * B * (2 * T.N * T.nc + 2 * d * d)), launch)
     return dT
 
 
@@ -1380,12 +1329,9 @@ def hutch_cg(jtj, eps, max_iter, tol, min_iter=None):
     ec = eps.contiguous()
     launch = lambda: _lib.check(_lib.load().cmf_hutch_cg(_p(jtj), _p(ec), d, S, B, int(max_iter), int(min_iter), float(tol), _p(u),
                                                          _p(w), _p(val), _p(iters), _stream()), "cmf_hutch_cg")
-    TIMER = _timer()
-    if TIMER is None or (d <= WIDE_NC and S <= WIDE_NC):
-        launch()
-    else:                                          # per iteration (at most max_iter) one G read per 16-probe chunk
-        TIMER.wrap("hutch_cg_wide", 2.0 * B * d * d * S * (max_iter + 1),
-                   4.0 * B * d * d * -(-S // 16) * (max_iter + 1), launch)
+    # per iteration (at most max_iter) one G read per 16-probe chunk
+    _timed("hutch_cg_wide" if d > WIDE_NC or S > WIDE_NC else None,
+           lambda: (2.0 * B * d * d * S * (max_iter + 1), 4.0 * B * d * d * -(-S // 16) * (max_iter + 1)), launch)
     return val, u, w, iters
 
 
@@ -1410,11 +1356,8 @@ def hutch_cotangent(u, eps, w, g_val=None, g_off=None, g_diag=None):
     uc, ec, wc = u.contiguous(), eps.contiguous(), w.contiguous()
     launch = lambda: _lib.check(_lib.load().cmf_hutch_cotangent(_p(uc), _p(ec), _p(wc), d, S, B, *[None if g is None else _p(g) for g in gs],
                                                                 _p(M), _stream()), "cmf_hutch_cotangent")
-    TIMER = _timer()
-    if TIMER is None or (d <= WIDE_NC and S <= WIDE_NC):
-        launch()
-    else:
-        TIMER.wrap("hutch_cotangent_wide", 2.0 * B * d * d * S, 4.0 * B * (3 * d * S + d * d), launch)
+    _timed("hutch_cotangent_wide" if d > WIDE_NC or S > WIDE_NC else None,
+           lambda: (2.0 * B * d * d * S, 4.0 * B * (3 * d * S + d * d)), launch)
     return M
 
 
@@ -1543,14 +1486,14 @@ def mlp_coupler(net, z, T, view, maps, decode, lj=None, ncols=None):
     a.lj = _p(lj)
     a.ncols = int(ncols) if (T is not None and ncols is not None) else 15
     launch = lambda: _lib.check(_lib.load().cmf_mlp_coupler(C.byref(a), _stream()), "cmf_mlp_coupler")
-    TIMER = _timer()
-    if TIMER is None:
-        return launch()
-    # algorithmic work: 2 in out FLOP per layer and column (1 primal + ncols tangents, or 1 per sample in primal mode)
-    cols = (1 + (ncols if ncols is not None else 15)) if T is not None else 1
-    fl = 2.0 * B * cols * sum(widths[i] * widths[i + 1] for i in range(len(widths) - 1))
-    by = 4.0 * B * cols * (view.cin + 2 * maps["n"])
-    TIMER.wrap("mlp_coupler" + ("_tangent" if T is not None else "_primal"), fl, by, launch)
+
+    def cost():
+        # algorithmic work: 2 in out FLOP per layer and column (1 primal + ncols tangents, or 1 per sample in primal mode)
+        cols = (1 + (ncols if ncols is not None else 15)) if T is not None else 1
+        fl = 2.0 * B * cols * sum(widths[i] * widths[i + 1] for i in range(len(widths) - 1))
+        by = 4.0 * B * cols * (view.cin + 2 * maps["n"])
+        return fl, by
+    return _timed("mlp_coupler" + ("_tangent" if T is not None else "_primal"), cost, launch)
 
 
 def made_masked_weight(weight, kind, features, multiplier=1):
@@ -1961,12 +1904,12 @@ def probe_apply(R, r_np, r_px, T, t_off, t_np, t_c, t_px, cls, y, y_np, y_px, np
         a.ymask, a.ymask_np = _p(ymask.data), int(ymask.np_bytes)
     a.np, a.cin, a.H, a.W, a.nc, a.ns = int(np_), int(cin), int(H), int(W), int(nc), int(ns)
     launch = lambda: _lib.check(_lib.load().cmf_probe_apply(C.byref(a), _stream()), "cmf_probe_apply")
-    TIMER = _timer()
-    if TIMER is None:
-        return launch()
-    # <= 13 cin FMAs per output element; u0 is written and R read once (counted whole: the live fraction is data)
-    px = float(H) * W * np_
-    TIMER.wrap(f"probe_apply_ci{cin}", 2.0 * PROBE_CLASSES * cin * 64 * nc * px, 4.0 * px * 64 * (nc + 16 * ns), launch)
+
+    def cost():
+        # <= 13 cin FMAs per output element; u0 is written and R read once (counted whole: the live fraction is data)
+        px = float(H) * W * np_
+        return 2.0 * PROBE_CLASSES * cin * 64 * nc * px, 4.0 * px * 64 * (nc + 16 * ns)
+    return _timed(f"probe_apply_ci{cin}", cost, launch)
 
 
 def seed_plane(H, W):
@@ -1983,11 +1926,7 @@ def seed_panel(T, view, H, W):
     v = C.c_void_p(T.data.data_ptr() + 4 * int(view.chan_off * HW * nc))
     launch = lambda: _lib.check(_lib.load().cmf_seed_panel(v, T.t_b, nc, _p(view.mask), _p(out), nc * col, col, B, H, W, nc, _stream()),
                                 "cmf_seed_panel")
-    TIMER = _timer()
-    if TIMER is None:
-        launch()
-    else:
-        TIMER.wrap("seed_panel", 0.0, 4.0 * B * nc * (col + HW), launch)
+    _timed("seed_panel", lambda: (0.0, 4.0 * B * nc * (col + HW)), launch)
     return dict(panel=out, np=nc * col, col=col)
 
 

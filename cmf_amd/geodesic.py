@@ -33,7 +33,7 @@ import torch
 
 from . import engine as E
 from .metric_stats import metric_head
-from .projection import DAMPING_MAX, DAMPING_MIN, ManifoldProjector
+from .projection import ManifoldProjector, join_parts, lm_loop, to_data_space
 
 __all__ = ["ManifoldGeodesic"]
 
@@ -121,7 +121,7 @@ class ManifoldGeodesic:
                              f"samples a decode sweep may hold; use fewer points")
         with E.scope(self.head.kernels):
             parts = [self._connect(z0[i:i + chunk], z1[i:i + chunk], steps) for i in range(0, B, chunk)]
-        return parts[0] if len(parts) == 1 else {k: torch.cat([p[k] for p in parts]) for k in parts[0]}
+        return join_parts(parts)
 
     def _connect(self, z0, z1, steps):
         prog, B, dev, P = self.head.program, z0.shape[0], z0.device, self.points
@@ -129,36 +129,28 @@ class ManifoldGeodesic:
         tt = torch.arange(P, dtype=torch.float32, device=dev) / N
         z = z0[:, None, :] + tt[None, :, None] * (z1 - z0)[:, None, :]          # the straight latent line
         z[:, N] = z1
-        decode = lambda zz: prog.decode(zz.reshape(-1, d), tangents=False)[0].contiguous()
-        x_hat = decode(z)
-        seg2, total, _ = E.curve_energy(x_hat, P)
-        energy = total * N
-        seg2_0, energy_0 = seg2.clone(), energy.clone()
-        lam = torch.full((B,), self.damping, dtype=torch.float64, device=dev)
-        accepted = torch.zeros(B, dtype=torch.int32, device=dev)
-        wide = (B,) + (1,) * (x_hat.dim())                                      # over (B, P, *x_shape)
         curves = lambda x: x.view(B, P, *x.shape[1:])
-        for _ in range(steps):
-            r = self.evaluate(z, lam)
+
+        def at(z):                                              # the state of ``lm_loop``: (z, g(z) as (B, P, *x_shape), ||r_i||^2, E)
+            x_hat = prog.decode(z.reshape(-1, d), tangents=False)[0].contiguous()
+            seg2, total, _ = E.curve_energy(x_hat, P)
+            return z, curves(x_hat), seg2, total * N
+
+        def trial(state, lam):
+            r = self.evaluate(state[0], lam)
             solved = r.info == 0
-            z_new = z.clone()
+            z_new = state[0].clone()
             z_new[:, 1:N] += torch.where(solved[:, None, None], r.delta, torch.zeros_like(r.delta)).float()
-            x_new = decode(z_new)
-            seg2_new, total_new, _ = E.curve_energy(x_new, P)
-            energy_new = total_new * N
-            ok = solved & (energy_new < energy)                                 # a NaN energy compares false: rejected
-            z = torch.where(ok[:, None, None], z_new, z)
-            x_hat = torch.where(ok.view(wide), curves(x_new), curves(x_hat)).view_as(x_hat)
-            seg2 = torch.where(ok[:, None], seg2_new, seg2)
-            energy = torch.where(ok, energy_new, energy)
-            lam = torch.where(ok, (lam * self.down).clamp_min(DAMPING_MIN), (lam * self.up).clamp_max(DAMPING_MAX))
-            accepted += ok
+            return solved, at(z_new)
+
+        state = at(z)
+        seg2_0, energy_0 = state[2].clone(), state[3].clone()
+        lam = torch.full((B,), self.damping, dtype=torch.float64, device=dev)
+        (z, x_hat, seg2, energy), lam, accepted = lm_loop(state, 3, lam, steps, self.up, self.down, trial)
         r = self.evaluate(z, torch.zeros_like(lam))
-        x_data = x_hat
-        for bijection in reversed(self.chain):
-            x_data = bijection.z_to_x(x_data)["x"]
+        x_data = to_data_space(self.chain, x_hat.flatten(0, 1))
         lengths, lengths_0 = seg2.sqrt(), seg2_0.sqrt()
-        return {"latents": z, "path_head": curves(x_hat), "path": curves(x_data), "energy": energy, "initial_energy": energy_0,
+        return {"latents": z, "path_head": x_hat, "path": curves(x_data), "energy": energy, "initial_energy": energy_0,
                 "length": lengths.sum(1), "initial_length": lengths_0.sum(1), "segment_lengths": lengths, "gradient": r.grad,
                 "gradient_max": r.stats[:, 3].contiguous(), "accepted": accepted, "damping": lam, "info": r.info}
 
@@ -259,7 +251,7 @@ class ManifoldGeodesic:
         v0 = v0.double().contiguous()
         with E.scope(self.head.kernels):
             parts = [self._shoot(z0[i:i + chunk].contiguous(), v0[i:i + chunk], steps, time, grads) for i in range(0, B, chunk)]
-        return parts[0] if len(parts) == 1 else {k: torch.cat([p[k] for p in parts]) for k in parts[0]}
+        return join_parts(parts)
 
     def _shoot(self, z0, v0, steps, time, grads):
         B, dev, h = z0.shape[0], z0.device, time / steps
@@ -303,9 +295,7 @@ class ManifoldGeodesic:
         speed = speed2.sqrt()
         done = torch.arange(steps, device=dev)[None, :] < taken[:, None]        # the steps a trajectory has taken
         length = h * torch.where(done, 0.5 * (speed[:, :-1] + speed[:, 1:]), torch.zeros_like(speed[:, 1:])).sum(1)
-        x_data = path_head.flatten(0, 1)
-        for bijection in reversed(self.chain):
-            x_data = bijection.z_to_x(x_data)["x"]
+        x_data = to_data_space(self.chain, path_head.flatten(0, 1))
         return {"latents": latents, "velocity": velocity, "momentum": momentum, "speed2": speed2, "length": length,
                 "path_head": path_head, "path": x_data.view(B, steps + 1, *x_data.shape[1:]), "steps_taken": taken, "info": info}
 
@@ -347,7 +337,7 @@ class ManifoldGeodesic:
                              f"{prog.tangent_chunk(B * P + 2)} samples a decode sweep may hold; use fewer points")
         with E.scope(self.head.kernels):
             parts = [self._transport(latents[i:i + chunk], w0[i:i + chunk]) for i in range(0, B, chunk)]
-        return parts[0] if len(parts) == 1 else {k: torch.cat([p[k] for p in parts]) for k in parts[0]}
+        return join_parts(parts)
 
     def _transport(self, latents, w0):
         prog = self.head.program

@@ -38,6 +38,35 @@ def wrapper_bijections(density, head):
     return chain
 
 
+def to_data_space(chain, x):
+    """The head-space tensor ``x`` mapped back to data space through the bijections ``chain`` (``wrapper_bijections``)."""
+    for bijection in reversed(chain):
+        x = bijection.z_to_x(x)["x"]
+    return x
+
+
+def join_parts(parts):
+    """The result dicts of a call's sub-batches as one dict, concatenated along the leading dimension."""
+    return parts[0] if len(parts) == 1 else {k: torch.cat([p[k] for p in parts]) for k in parts[0]}
+
+
+def lm_loop(state, cost, lam, steps, up, down, trial):
+    """The accept/reject loop of the damped Gauss-Newton tools (the projector's samples, the geodesic's curves).  ``state``: a
+    tuple of tensors with the unit -- sample or curve -- as leading dimension, of which ``state[cost]`` (units,) float64 is what the
+    steps lower; ``lam`` (units,) float64, the dampings.  ``trial(state, lam)`` proposes: (solved (units,) bool, new state).  A
+    unit accepts iff its solve succeeded and its cost strictly fell -- then it takes the new state, entry by entry, and lambda <-
+    max(lambda ``down``, DAMPING_MIN) --, else it stays and lambda <- min(lambda ``up``, DAMPING_MAX).  Returns (state, lam,
+    accepted (units,) int32, the steps each unit took)."""
+    accepted = torch.zeros(lam.shape[0], dtype=torch.int32, device=lam.device)
+    for _ in range(steps):
+        solved, new = trial(state, lam)
+        ok = solved & (new[cost] < state[cost])                       # a NaN cost compares false: rejected
+        state = tuple(torch.where(ok.view(-1, *[1] * (s.dim() - 1)), n, s) for n, s in zip(new, state))
+        lam = torch.where(ok, (lam * down).clamp_min(DAMPING_MIN), (lam * up).clamp_max(DAMPING_MAX))
+        accepted += ok
+    return state, lam, accepted
+
+
 class ManifoldProjector:
     """Damped Gauss-Newton projection onto the manifold of a non-square density with latent dimension <= 128.
 
@@ -97,32 +126,26 @@ class ManifoldProjector:
         chunk = prog.tangent_chunk(B)
         with E.scope(self.head.kernels):
             parts = [self._project(x[i:i + chunk], steps) for i in range(0, B, chunk)]
-        return parts[0] if len(parts) == 1 else {k: torch.cat([p[k] for p in parts]) for k in parts[0]}
+        return join_parts(parts)
 
     def _project(self, x, steps):
-        prog, B, dev = self.head.program, x.shape[0], x.device
+        prog = self.head.program
         y, z = self.head_input_and_latent(x)
-        x_hat = prog.decode(z, tangents=False)[0].contiguous()
-        d2, _ = E.residual_sqnorm(y, x_hat)
-        d2_0 = d2.clone()
-        lam = torch.full((B,), self.damping, dtype=torch.float64, device=dev)
-        accepted = torch.zeros(B, dtype=torch.int32, device=dev)
-        wide = (B,) + (1,) * (x_hat.dim() - 1)
-        for _ in range(steps):
-            r = self.evaluate(y, z, lam)
+
+        def at(z):                                                    # the state of ``lm_loop``: (z, g(z), ||y - g(z)||^2)
+            x_hat = prog.decode(z, tangents=False)[0].contiguous()
+            return z, x_hat, E.residual_sqnorm(y, x_hat)[0]
+
+        def trial(state, lam):
+            r = self.evaluate(y, state[0], lam)
             solved = r.info == 0
-            z_new = z + torch.where(solved[:, None], r.delta, torch.zeros_like(r.delta)).float()
-            x_new = prog.decode(z_new, tangents=False)[0].contiguous()
-            d2_new, _ = E.residual_sqnorm(y, x_new)
-            ok = solved & (d2_new < d2)                               # a NaN distance compares false: rejected
-            z = torch.where(ok[:, None], z_new, z)
-            x_hat = torch.where(ok.view(wide), x_new, x_hat)
-            d2 = torch.where(ok, d2_new, d2)
-            lam = torch.where(ok, (lam * self.down).clamp_min(DAMPING_MIN), (lam * self.up).clamp_max(DAMPING_MAX))
-            accepted += ok
+            return solved, at(state[0] + torch.where(solved[:, None], r.delta, torch.zeros_like(r.delta)).float())
+
+        state = at(z)
+        d2_0 = state[2].clone()
+        lam = torch.full((x.shape[0],), self.damping, dtype=torch.float64, device=x.device)
+        (z, x_hat, d2), lam, accepted = lm_loop(state, 2, lam, steps, self.up, self.down, trial)
         r = self.evaluate(y, z, torch.zeros_like(lam))
-        x_data = x_hat
-        for bijection in reversed(self.chain):
-            x_data = bijection.z_to_x(x_data)["x"]
-        return {"latent": z, "reconstruction_head": x_hat, "reconstruction": x_data, "distance2": d2, "initial_distance2": d2_0,
-                "tangential2": r.stats[:, 1].contiguous(), "gradient": r.grad, "accepted": accepted, "damping": lam, "info": r.info}
+        return {"latent": z, "reconstruction_head": x_hat, "reconstruction": to_data_space(self.chain, x_hat), "distance2": d2,
+                "initial_distance2": d2_0, "tangential2": r.stats[:, 1].contiguous(), "gradient": r.grad, "accepted": accepted,
+                "damping": lam, "info": r.info}
