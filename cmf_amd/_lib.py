@@ -114,6 +114,9 @@ SIGNATURES = {
     "cmf_curve_step": (_i, [_fp, _ll, _ll, _i, _i, _i, _i, _i, _fp, _fp, _fp, _fp, _fp, _fp, _fp, _fp, _fp, _fp, _ll, _fp]),
     "cmf_metric_solve": (_i, [_fp, _fp, _i, _i, _i, _fp, _fp, _fp, _fp, _fp]),
     "cmf_transport_chain": (_i, [_fp, _fp, _fp, _i, _i, _i, _i, _fp, _fp, _fp, _fp, _fp, _fp]),
+    "cmf_star_step_ws": (_ll, [_i, _i, _i, _i]),
+    "cmf_star_step": (_i, [_fp, _ll, _ll, _i, _i, _i, _i, _i, _i, _ll, _fp, _fp, _fp, _fp, _fp, _fp, _fp, _fp, _fp, _fp, _fp, _fp, _fp,
+                           _ll, _fp]),
     "cmf_stanh_backward": (_i, [_fp, _fp, _fp, _fp, _fp, _fp, _fp, _fp, _fp, _i, _i, _i, _fp]),
     "cmf_tanh_cross_terms": (_i, [_fp, _ll, _ll, _fp, _ll, _ll, _fp, _fp, _i, _i, _i, _fp]),
     "cmf_tanh_backward": (_i, [_fp, _fp, _fp, _ll, _fp, _fp]),

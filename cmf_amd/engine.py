@@ -1190,6 +1190,115 @@ def curve_step(T, jtj, cross, xhat, points, damping):
     return r
 
 
+#: most arms of a star ``star_step`` takes (csrc/star_step.hip: the centre kernel reads the arms' codes with one thread each)
+STAR_MAX_ARMS = 64
+
+
+class StarStepResult:
+    """Outputs of ``star_step`` (all on the device, float64 unless noted) for stars of K arms of P points, N = P - 1 segments and
+    M = P - 2 interior points per arm: ``grad`` (stars, K, M, d) = w_k g_{k,i} and ``grad_centre`` (stars, d) = sum_k w_k g^c_k,
+    ``delta`` (stars, K, M, d) and ``delta_centre`` (stars, d), ``seg2`` (stars, K, N) = ||r_i||^2, ``stats`` (stars, 4) =
+    [sum_k w_k sum_i ||r_i||^2, g^T delta, delta^T H delta, max |g| over arms and centre], ``info`` (stars,) int32 (0 ok, 1
+    non-positive pivot in an arm or at the centre: delta, delta_centre and stats[:, 1:3] NaN, 2 non-finite input: everything NaN)."""
+    __slots__ = ("grad", "grad_centre", "delta", "delta_centre", "seg2", "stats", "info")
+
+
+def star_cross_gram(T, d):
+    """The cross-Gram blocks ``star_step`` reads, from the unpadded stack ``T`` of n >= 3 samples: (n - 1, d, d) float32 with block
+    q = J_q^T J_{q+1} for q = 1 .. n - 2 and block 0 -- the pair of the first arm's fixed end, which no star reads -- zero.  Two
+    ``cmf_cross_gram`` launches on views of the stack as one curve -- all n samples (the pairs 1 .. n - 3), and the last three
+    samples with one more behind them that, as a curve's end point, is never read (the pair n - 2) --, so that the decode sweep
+    needs no padding samples.  The same arithmetic per pair as ``cross_gram``; no synchronisation."""
+    _check_tangent(T)
+    _check_on_gpu("T", T.data)
+    d, n = int(d), T.B
+    _check_width(d, "the curve kernels support", GEODESIC_MAX_WIDTH)
+    if n < 3 or T.nc % 16 or T.nc < d or T.nc > GEODESIC_MAX_WIDTH:
+        raise ValueError(f"T (B = {n}, nc = {T.nc}) must hold at least 3 samples and d = {d} <= nc <= {GEODESIC_MAX_WIDTH} columns, "
+                         f"nc % 16 == 0")
+    out = torch.empty(n - 1, d, d, dtype=torch.float32, device=T.data.device)
+    out[0].zero_()
+    lib = _lib.load()
+    at = lambda sample: C.c_void_p(T.data.data_ptr() + 4 * sample * T.t_b)
+    block = lambda q: C.c_void_p(out.data_ptr() + 4 * q * d * d)
+
+    def launch():
+        if n > 3:
+            _lib.check(lib.cmf_cross_gram(at(0), T.t_b, T.t_r, T.N, T.nc, d, n, 1, block(1), _stream()), "cmf_cross_gram")
+        _lib.check(lib.cmf_cross_gram(at(n - 3), T.t_b, T.t_r, T.N, T.nc, d, 4, 1, block(n - 2), _stream()), "cmf_cross_gram")
+    _timed("cross_gram", lambda: ((n - 2) * 2.0 * T.N * d * d, 4.0 * (n - 2) * (2 * T.N * T.nc + d * d)), launch)
+    return out
+
+
+def star_step(T, jtj, cross, xhat, points, arms, weights, damping, first=0):
+    """One damped Gauss-Newton step per star: ``arms`` = K curves of ``points`` points that share a free end point.
+    The stack is star-major, then arm-major, point 0 the arm's fixed end and point P - 1 the arm's own copy of the centre:
+    ``jtj`` (stars * K * P, d, d) float32 (one ``gram_cholesky`` attempt; lower triangles read), ``cross`` (stars * K * P - 1, d, d)
+    float32, block q = J_q^T J_{q+1} of neighbouring samples of the stack (``cross_gram`` on a sweep padded by one sample at each
+    end; the blocks that straddle two arms are not read), ``xhat`` (stars * K * P, ...) float32, ``weights`` (stars, K) float64,
+    finite and > 0, ``damping`` (stars,) float64 >= 0.  The Jacobian stack ``T`` holds the stack from its sample ``first`` on.  In
+    float64: the gradient of sum_k w_k 1/2 sum_i ||r_{k,i}||^2 over the interior points and the centre, and delta = (H + damping
+    diag H)^-1 grad on the block-arrow Gauss-Newton matrix, arm by arm with only the centre block shared.  Returns a
+    ``StarStepResult``; its sums over arms are taken in arm order.  Deterministic per star; three launches, no synchronisation."""
+    points, K, first = int(points), int(arms), int(first)
+    if not 1 <= K <= STAR_MAX_ARMS:
+        raise ValueError(f"arms = {K}: a star has 1 <= arms <= {STAR_MAX_ARMS}")
+    _check_tensor("xhat", xhat, torch.float32, "(stars * arms * points, ...)", lambda t: t.dim() >= 2)
+    rows, dev = xhat.shape[0], xhat.device
+    stars = _whole_curves(points, rows, "xhat") // K
+    n = int(np.prod(xhat.shape[1:]))
+    if rows != stars * K * points or n < 1:
+        raise ValueError(f"the {rows} samples of xhat {tuple(xhat.shape)} must be whole stars of {K} arms of {points} points with at "
+                         f"least one element per point")
+    _, d = _gram_stack(jtj, "stars * arms * points", "the star kernels support", GEODESIC_MAX_WIDTH)
+    _check_tangent(T)
+    _check_on_gpu("T", T.data)
+    if T.nc % 16 or T.nc < d or T.nc > GEODESIC_MAX_WIDTH:
+        raise ValueError(f"T (nc = {T.nc}) must hold d = {d} <= nc <= {GEODESIC_MAX_WIDTH} columns, nc % 16 == 0")
+    _check_tensor("cross", cross, torch.float32, f"({max(rows - 1, 0)}, {d}, {d})", lambda t: t.shape == (max(rows - 1, 0), d, d))
+    if first < 0 or T.B < first + rows or T.N != n or jtj.shape[0] != rows or T.data.device != dev or jtj.device != dev or \
+            cross.device != dev:
+        raise ValueError(f"T (B = {T.B}, N = {T.N}, nc = {T.nc}) on {T.data.device} must hold d = {d} <= nc columns, nc % 16 == 0, "
+                         f"for the {rows} samples of {n} elements of xhat on {dev} from its sample {first} on, like jtj "
+                         f"{tuple(jtj.shape)} on {jtj.device} and cross on {cross.device}")
+    _check_tensor("weights", weights, torch.float64, f"({stars}, {K})", lambda t: t.shape == (stars, K), dev)
+    _check_damping(damping, stars, dev)
+    M, N = points - 2, points - 1
+    f64 = lambda *shape: torch.empty(*shape, dtype=torch.float64, device=dev)
+    r = StarStepResult()
+    r.grad, r.delta, r.grad_centre, r.delta_centre = f64(stars, K, M, d), f64(stars, K, M, d), f64(stars, d), f64(stars, d)
+    r.seg2, r.stats = f64(stars, K, N), f64(stars, 4)
+    r.info = torch.empty(stars, dtype=torch.int32, device=dev)
+    if stars == 0:
+        return r
+    lib = _lib.load()
+    need = lib.cmf_star_step_ws(d, points, K, stars)
+    _lib.check(min(need, 0), "cmf_star_step_ws")
+    ws, arm = f64(need), f64(stars, K, 4)
+    launch = lambda: _lib.check(lib.cmf_star_step(_p(T.data), T.t_b, T.t_r, n, T.nc, d, points, K, stars, first, _p(jtj), _p(cross),
+                                                  _p(xhat), _p(weights), _p(damping), _p(r.grad), _p(r.grad_centre), _p(r.delta),
+                                                  _p(r.delta_centre), _p(arm), _p(r.seg2), _p(r.info), _p(ws), need, _stream()),
+                                "cmf_star_step")
+
+    def cost():
+        # float64 per arm: curve_step's terms with M + 1 streams of J and M full window eliminations; per star the centre's sums
+        # 3 K d^2 / 2, its elimination d^3 / 3 and substitutions 2 d^2; bytes: as curve_step per arm, with T_k and r_k out and in
+        ncl = min(T.nc, -(-d // 4) * 4)
+        return (stars * K * (N * 2.0 * n * d + M * (7.0 * d ** 3 / 3.0 + 11.0 * d * d) + 3.0 * N * n + 1.5 * d * d)
+                + stars * (1.5 * K * d * d + d ** 3 / 3.0 + 2.0 * d * d),
+                stars * K * (N * (4.0 * n * ncl + 12.0 * n + 12.0 * d * d) + M * (8.0 * d * d + 16.0 * (2 * d + 1) * d + 16.0 * d)
+                             + 8.0 * points * n + 8.0 * points + 8.0 * d * d + 32.0 * d + 40.0) + stars * (16.0 * d + 4.0))
+    _timed("star_step", cost, launch)
+    # the star's figures from the arms', summed in arm order
+    total = [torch.zeros(stars, dtype=torch.float64, device=dev) for _ in range(3)]
+    for k in range(K):
+        for j in range(3):
+            total[j] = total[j] + weights[:, k] * arm[:, k, j]
+    gmax = torch.maximum((weights * arm[:, :, 3]).amax(1), r.grad_centre.abs().amax(1))
+    r.stats = torch.stack(total + [gmax], 1)
+    return r
+
+
 #: widest metric ``metric_solve`` takes: the float64 matrix of a sample lives in LDS (csrc/shoot_step.hip)
 SHOOT_MAX_WIDTH = 128
 

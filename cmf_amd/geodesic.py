@@ -26,6 +26,14 @@ with the inverse of the projection back (csrc/transport_step.hip, float64 per cu
     tr = geo.transport(x0, x1, w)                        # connect + w (B, d) or (B, d, m) at x0 carried to x1
     tr["transported"], tr["norm2"]                       # (B, d, m) at x1; w^T G w at every point of the curve
     out = geo.analogy(xa, xb, xc)                        # "a is to b as c is to ?": out["path"][:, -1]
+
+``mean`` takes more than two inputs: the Frechet (Karcher) mean of K inputs, their weighted barycentre on the
+manifold.  It relaxes the whole star -- K discretised arms that share one free end point -- at once; a step is one decode sweep over
+the stars and a float64 solve of the block-arrow normal equations, arm by arm with only the centre block shared
+(csrc/star_step.hip).
+
+    out = geo.mean(xs, weights)                          # xs (B, K, *x_shape): out["mean"] (B, *x_shape) in data space
+    out["distances"], out["variance"]                    # (B, K) arm lengths; the estimate of the Frechet variance
 """
 import math
 
@@ -50,7 +58,10 @@ class ManifoldGeodesic:
     RK4 steps (``log`` / ``log_latents``: ``connect`` plus the velocity that takes ``shoot`` from the first end to the second).
 
     ``transport`` / ``transport_latents`` carry latent tangent vectors along a curve by parallel transport; ``analogy`` carries the
-    ``log`` velocity of one pair of inputs to a third input and shoots along it there."""
+    ``log`` velocity of one pair of inputs to a third input and shoots along it there.
+
+    ``mean`` / ``mean_latents`` find the weighted Frechet mean of K inputs: the loop above with a star of K arms of ``points``
+    latents and one shared free end point as its unit."""
 
     def __init__(self, density, points=17, steps=10, damping=1e-3, up=10.0, down=0.1, shoot_steps=16):
         if int(shoot_steps) < 1:
@@ -152,6 +163,125 @@ class ManifoldGeodesic:
         lengths, lengths_0 = seg2.sqrt(), seg2_0.sqrt()
         return {"latents": z, "path_head": x_hat, "path": curves(x_data), "energy": energy, "initial_energy": energy_0,
                 "length": lengths.sum(1), "initial_length": lengths_0.sum(1), "segment_lengths": lengths, "gradient": r.grad,
+                "gradient_max": r.stats[:, 3].contiguous(), "accepted": accepted, "damping": lam, "info": r.info}
+
+    # -- Frechet means ---------------------------------------------------------------------------
+    def evaluate_star(self, z, weights, lam):
+        """Decode with tangents at the stars ``z`` (B, K, P, d) -- one sweep over the star-major stack --, Gram, the cross-Gram blocks
+        of its neighbouring samples (``engine.star_cross_gram``: no padding samples in the sweep), star step kernels: the
+        ``engine.StarStepResult``."""
+        prog = self.head.program
+        B, K, P, d = z.shape
+        x_hat, T = prog.decode(z.reshape(B * K * P, d), tangents=True)
+        jtj = E.gram_cholesky(T, d, 1).jtj
+        return E.star_step(T, jtj, E.star_cross_gram(T, d), x_hat.contiguous(), P, K, weights, lam)
+
+    @torch.no_grad()
+    def mean(self, xs, weights=None, steps=None):
+        """The Frechet (Karcher) mean of the K inputs ``xs[b]`` for every b (``xs``: (B, K, *x_shape), the density's inputs as for
+        ``connect``; never modified, no dequantisation noise is drawn): ``mean_latents`` of the encoder's latents."""
+        if not isinstance(xs, torch.Tensor) or xs.dim() < 3:
+            raise ValueError(f"xs must be (B, K, *x_shape), got {tuple(getattr(xs, 'shape', ()))}")
+        if xs.shape[0] == 0 or xs.shape[1] == 0:
+            raise ValueError(f"mean needs at least one group of at least one input, got xs {tuple(xs.shape)}")
+        E.require_gpu(xs, "xs")
+        with E.scope(self.head.kernels):
+            z = self.projector.head_input_and_latent(xs.flatten(0, 1))[1]
+        return self.mean_latents(z.view(xs.shape[0], xs.shape[1], -1), weights, steps)
+
+    @staticmethod
+    def _star_weights(weights, B, K):
+        """``weights`` as given ((B, K) or (K,), floating point, finite and > 0; None: all ones) or a ValueError.  The values are
+        looked at where they are: weights on the device make the call wait for them once."""
+        if weights is None:
+            return None
+        if not isinstance(weights, torch.Tensor) or not weights.is_floating_point() or tuple(weights.shape) not in ((B, K), (K,)):
+            raise ValueError(f"weights must be a floating point tensor of shape ({B}, {K}) or ({K},), got "
+                             f"{tuple(getattr(weights, 'shape', ()))} {getattr(weights, 'dtype', type(weights).__name__)}")
+        if not bool((torch.isfinite(weights) & (weights > 0)).all()):
+            raise ValueError("weights must be finite and > 0")
+        return weights
+
+    @torch.no_grad()
+    def mean_latents(self, zs, weights=None, steps=None):
+        """The weighted Frechet mean of the head's latents ``zs`` (B, K, d) float32 per group b: the point m that minimises
+        sum_k w_k dist(m, z_k)^2 in the pull-back metric, found by relaxing the whole star at once -- K discretised arms of P =
+        ``points`` latents from the inputs to one shared free end point, the centre --, E = sum_k w_k N sum_i ||r_{k,i}||^2 over all
+        interior points and the centre by the damped Gauss-Newton loop of ``connect`` with the star as unit.  ``weights``: (B, K) or
+        (K,), floating point, finite and > 0, used as given (not normalised); default all ones.  The start is the centre at
+        sum_k w_k z_k / sum_k w_k with every arm on the straight latent line.  Returns device tensors for the B stars of K arms with
+        N = P - 1 segments and M = P - 2 interior points each:
+          ``mean_latent`` (B, d) float32; ``mean_head`` (B, *x_shape) = g(mean_latent) in the head's input space and ``mean``, the
+          same mapped back to data space; ``latents`` (B, K, P, d) float32 (``[:, k, 0]`` = z_k, ``[:, k, -1]`` = mean_latent);
+          ``path_head`` and ``path`` (B, K, P, ...); ``distances`` and ``initial_distances`` (B, K) float64, the arm lengths sum_i
+          ||r_{k,i}|| of the returned star and of the start; ``segment_lengths`` (B, K, N) float64; ``energy`` and
+          ``initial_energy`` (B,) float64; ``variance`` (B,) float64 = energy / sum_k w_k, the estimate of the Frechet variance;
+          ``gradient`` (B, K, M, d) and ``gradient_centre`` (B, d) float64 at the returned star and ``gradient_max`` (B,) their
+          largest magnitude; ``accepted`` (B,) int32; ``damping`` (B,) float64; ``info`` (B,) int32, the code of the closing
+          evaluation (``engine.star_step``).
+        Sub-batches of whole stars; enqueues kernels only -- beyond the look at ``weights`` no copy to the
+        host, no synchronisation -- and leaves ``head.last_gram`` alone."""
+        prog, P = self.head.program, self.points
+        if not isinstance(zs, torch.Tensor) or zs.dim() != 3 or zs.shape[2] != prog.d or zs.dtype != torch.float32:
+            raise ValueError(f"zs must be (B, K, {prog.d}) float32, got {tuple(getattr(zs, 'shape', ()))} "
+                             f"{getattr(zs, 'dtype', type(zs).__name__)}")
+        B, K = zs.shape[0], zs.shape[1]
+        steps = self.steps if steps is None else int(steps)
+        if B == 0 or steps < 0 or not 1 <= K <= E.STAR_MAX_ARMS:
+            raise ValueError(f"mean needs at least one group of 1 <= K <= {E.STAR_MAX_ARMS} inputs and steps >= 0, got {B} groups "
+                             f"of {K} and steps = {steps}")
+        weights = self._star_weights(weights, B, K)
+        E.require_gpu(zs, "zs")
+        dev = zs.device
+        if weights is None:
+            w = torch.ones(B, K, dtype=torch.float64, device=dev)
+        else:
+            w = weights.to(device=dev, dtype=torch.float64).expand(B, K).contiguous()
+        chunk = prog.tangent_chunk(B * K * P) // (K * P)
+        if chunk == 0:
+            raise ValueError(f"points = {P}: one star of {K} inputs with {P} points per arm does not fit the sub-batch of "
+                             f"{prog.tangent_chunk(B * K * P)} samples a decode sweep may hold; use fewer points or fewer inputs")
+        with E.scope(self.head.kernels):
+            parts = [self._mean(zs[i:i + chunk], w[i:i + chunk].contiguous(), steps) for i in range(0, B, chunk)]
+        return join_parts(parts)
+
+    def _mean(self, zs, w, steps):
+        prog, dev, P = self.head.program, zs.device, self.points
+        B, K, d = zs.shape
+        N = P - 1
+        arm_sum = lambda t: sum((w[:, k] * t[:, k] for k in range(1, K)), w[:, 0] * t[:, 0])      # (B, K) -> (B,), in arm order
+        w_sum = arm_sum(torch.ones_like(w))
+        zc = (sum((w[:, k, None] * zs[:, k].double() for k in range(1, K)), w[:, 0, None] * zs[:, 0].double()) / w_sum[:, None]).float()
+        tt = torch.arange(P, dtype=torch.float32, device=dev) / N
+        z = zs[:, :, None, :] + tt[None, None, :, None] * (zc[:, None, :] - zs)[:, :, None, :]       # straight latent arms
+        z[:, :, N] = zc[:, None, :]
+        stars = lambda x: x.view(B, K, P, *x.shape[1:])
+
+        def at(z):                                              # the state of ``lm_loop``: (z, g(z), ||r_{k,i}||^2, E)
+            x_hat = prog.decode(z.reshape(-1, d), tangents=False)[0].contiguous()
+            seg2, total, _ = E.curve_energy(x_hat, P)
+            return z, stars(x_hat), seg2.view(B, K, N), arm_sum(total.view(B, K)) * N
+
+        def trial(state, lam):
+            r = self.evaluate_star(state[0], w, lam)
+            solved = r.info == 0
+            z_new = state[0].clone()
+            z_new[:, :, 1:N] += torch.where(solved[:, None, None, None], r.delta, torch.zeros_like(r.delta)).float()
+            z_new[:, :, N] += torch.where(solved[:, None], r.delta_centre, torch.zeros_like(r.delta_centre)).float()[:, None, :]
+            return solved, at(z_new)
+
+        state = at(z)
+        seg2_0, energy_0 = state[2].clone(), state[3].clone()
+        lam = torch.full((B,), self.damping, dtype=torch.float64, device=dev)
+        (z, x_hat, seg2, energy), lam, accepted = lm_loop(state, 3, lam, steps, self.up, self.down, trial)
+        r = self.evaluate_star(z, w, torch.zeros_like(lam))
+        x_data = to_data_space(self.chain, x_hat.flatten(0, 2))
+        lengths, lengths_0 = seg2.sqrt(), seg2_0.sqrt()
+        path = stars(x_data)
+        return {"mean_latent": z[:, 0, N].contiguous(), "mean_head": x_hat[:, 0, N].contiguous(), "mean": path[:, 0, N].contiguous(),
+                "latents": z, "path_head": x_hat, "path": path, "distances": lengths.sum(2),
+                "initial_distances": lengths_0.sum(2), "segment_lengths": lengths, "energy": energy, "initial_energy": energy_0,
+                "variance": energy / w_sum, "gradient": r.grad, "gradient_centre": r.grad_centre,
                 "gradient_max": r.stats[:, 3].contiguous(), "accepted": accepted, "damping": lam, "info": r.info}
 
     # -- the exponential map (DESIGN 4.3h) -----------------------------------------------------------------

@@ -530,6 +530,38 @@ int cmf_metric_solve(const float* jtj, const double* rhs, int d, int B, int appl
  * aligned, the others 4-byte.  Anything else: CMF_EINVAL.  No allocation, no synchronisation.                                  */
 int cmf_transport_chain(const float* jtj, const float* cross, const double* w0, int d, int m, int points, int curves, double* out,
                         double* fwd, double* bwd, double* norm2, int* info, void* stream);
+/* One damped Gauss-Newton step on whole stars: `arms` = K discretised curves of `points` = P >= 3 points that share one free end
+ * point, the centre.  The stack is star-major, then arm-major: point i of arm k of star s is sample q = (s K + k) P + i
+ * of jtj and xhat and sample first + q of the Jacobian stack t (first >= 0: a sweep padded in front needs no copy).  Point 0 is the
+ * arm's fixed end, point N = P - 1 the arm's own copy of the centre, M = P - 2 interior points.  Per arm, unweighted:
+ *   g_i = J_i^T (xhat_{i-1} + xhat_{i+1} - 2 xhat_i), i = 1 .. M;  g^c_k = J_N^T (xhat_M - xhat_N);
+ *   H_ii = 2 J_i^T J_i, H_{i,i+1} = -C_i = -J_i^T J_{i+1} for i = 1 .. M, centre contribution J_N^T J_N.
+ * The star is sum_k weights[s][k] (that of arm k), A = H + damping[s] diag(H), delta = A^-1 g, in float64.
+ *   jtj [stars K P][d][d] float32 as ONE cmf_gram_cholesky attempt leaves it: the lower triangles of the points 1 .. N are read;
+ *   cross [stars K P - 1][d][d] float32: block q = J_q^T J_{q+1} of neighbouring samples of the stack, as cmf_cross_gram gives them
+ *     for a stack padded by one sample at each end (the blocks that straddle two arms and those of the points 0 are not read);
+ *   xhat [stars K P][n_rows] float32; weights [stars][K] float64, finite and > 0; damping [stars] float64, >= 0.
+ *   grad [stars][K][M][d] = weights_k g_{k,i};  grad_centre [stars][d] = sum_k weights_k g^c_k, summed in arm order;
+ *   delta [stars][K][M][d];  delta_centre [stars][d];  seg2 [stars][K][N] = ||r_i||^2, the bits of cmf_curve_step's on the arm;
+ *   arm_stats [stars][K][4] = { sum_i ||r_i||^2, g_k^T delta_k, delta^T H_k delta, max_i |g_{k,i}| } of the unweighted arm, the
+ *     two forms with the arm's centre terms g^c_k^T delta_centre and delta_centre^T J_N^T J_N delta_centre; the maximum is over the
+ *     interior points;
+ *   info [stars] int32: 0 ok; 1 a pivot of some arm or of the centre was not positive and finite (delta, delta_centre and the two
+ *     forms of every arm are NaN, the rest is valid); 2 a non-finite value in what is read, or a weight that is not finite and > 0
+ *     (every output of the star is NaN; takes precedence over 1).  Other stars are unaffected.
+ *   ws: caller-owned, 8-byte aligned, ws_doubles >= cmf_star_step_ws(d, points, arms, stars) doubles (CMF_EINVAL for arguments out
+ *     of range): per arm its Schur contribution to the centre block, the eliminated columns of every block and, for 64 < d, the
+ *     elimination window.
+ * Three launches: per arm forward, per star the centre, per arm backward.  A star's outputs are a function of its own inputs and
+ * of (n_rows, nc, d, P, K) alone: no atomics, independent of `stars`, of the star's position and of completion order, and they
+ * repeat bit for bit.
+ * 1 <= d <= 128, 1 <= arms <= 64, nc % 16 == 0, d <= nc, t_b and t_r >= nc and % 4 == 0, t 16-byte aligned, float64 pointers 8-byte
+ * aligned, the others 4-byte, no pointer NULL, n_rows, stars >= 1.  Anything else: CMF_EINVAL.  No allocation, no synchronisation. */
+long long cmf_star_step_ws(int d, int points, int arms, int stars);
+int cmf_star_step(const float* t, long long t_b, long long t_r, int n_rows, int nc, int d, int points, int arms, int stars,
+                  long long first, const float* jtj, const float* cross, const float* xhat, const double* weights,
+                  const double* damping, double* grad, double* grad_centre, double* delta, double* delta_centre, double* arm_stats,
+                  double* seg2, int* info, double* ws, long long ws_doubles, void* stream);
 /* Reverse of the head above for training (autograd through non_square.py:307-308, :280-294, :87-100):
  *   dt(b, r, :) = 2 * t(b, r, :) * (g_logdet[b] * jtj_b^-1 + g_l1off[b] * sign(jtj_b)[i != j]
  *                                   + g_l1diag[b] * sign(jtj_b)[i == j])
