@@ -1299,6 +1299,58 @@ def star_step(T, jtj, cross, xhat, points, arms, weights, damping, first=0):
     return r
 
 
+#: widest metric ``tangent_pca`` takes: the float64 matrix of a group lives in LDS (csrc/tangent_pca.hip)
+TANGENT_PCA_MAX_WIDTH = 128
+
+
+class TangentPcaResult:
+    """Outputs of ``tangent_pca`` (all on the device, float64 unless noted) for groups of K tangent vectors and r components:
+    ``variances`` (B, r) descending, ``directions`` (B, r, d) = u_j, ``scores`` (B, K, r) = u_j^T G v_k, ``covectors`` (B, K, d) =
+    G v_k, ``norm2`` (B, K) = v_k^T G v_k, ``total`` (B,) = sum_k w_k norm2_k / sum_k w_k, ``rank`` and ``sweeps`` (B,) int32,
+    ``info`` (B,) int32 (0 ok, 1 sweep cap reached, 2 a non-finite input or a weight that is not finite and > 0: every float output
+    of the group NaN, rank 0)."""
+    __slots__ = ("variances", "directions", "scores", "covectors", "norm2", "total", "rank", "sweeps", "info")
+
+
+def tangent_pca(jtj, vectors, weights, components=None):
+    """Principal geodesic analysis per group: PCA of the K tangent vectors ``vectors`` (B, K, d) float64 with the
+    ``weights`` (B, K) float64, finite and > 0, in the metric ``jtj`` (B, d, d) float32 (one ``gram_cholesky`` attempt; lower
+    triangles read), in its dual K x K form by the float64 Jacobi method of ``gram_spectrum``, one workgroup per group.
+    ``components`` = r, 1 <= r <= K (default K), modes are returned; those beyond the numerical rank -- eigenvalues not above
+    d 2^-24 times the largest, which a float32 metric leaves undetermined -- have zero directions and scores.  Returns a
+    ``TangentPcaResult``.  Deterministic per group; enqueues one launch, no synchronisation."""
+    B, d = _gram_stack(jtj, "B", "the tangent PCA kernel supports", TANGENT_PCA_MAX_WIDTH)
+    dev = jtj.device
+    _check_tensor("vectors", vectors, torch.float64, f"({B}, K, {d})", lambda t: t.dim() == 3 and t.shape[0] == B and t.shape[2] == d,
+                  dev)
+    K = vectors.shape[1]
+    if not 1 <= K <= STAR_MAX_ARMS:
+        raise ValueError(f"vectors {tuple(vectors.shape)}: a group has 1 <= K <= {STAR_MAX_ARMS} tangent vectors")
+    _check_tensor("weights", weights, torch.float64, f"({B}, {K})", lambda t: t.shape == (B, K), dev)
+    r_ = K if components is None else int(components)
+    if not 1 <= r_ <= K:
+        raise ValueError(f"components = {components}: need 1 <= components <= K = {K}")
+    f64 = lambda *shape: torch.empty(*shape, dtype=torch.float64, device=dev)
+    i32 = lambda *shape: torch.empty(*shape, dtype=torch.int32, device=dev)
+    r = TangentPcaResult()
+    r.variances, r.directions, r.scores, r.covectors = f64(B, r_), f64(B, r_, d), f64(B, K, r_), f64(B, K, d)
+    r.norm2, r.total = f64(B, K), f64(B)
+    r.rank, r.sweeps, r.info = i32(B), i32(B), i32(B)
+    if B == 0:
+        return r
+    launch = lambda: _lib.check(_lib.load().cmf_tangent_pca(_p(jtj), _p(vectors), _p(weights), d, K, r_, B, _p(r.variances),
+                                                            _p(r.directions), _p(r.scores), _p(r.covectors), _p(r.norm2),
+                                                            _p(r.total), _p(r.rank), _p(r.sweeps), _p(r.info), _stream()),
+                                "cmf_tangent_pca")
+    # float64: G v_k 2 K d^2, the K (K + 1) / 2 dots of length d, a nominal 10 sweeps of K (K - 1) / 2 rotations of 6 FLOP on 3 K
+    # entry pairs (M twice, P once), the r directions 3 K d each; bytes: jtj, vectors (three times), weights in, the outputs out
+    # and covectors, directions in again
+    _timed("tangent_pca", lambda: (B * (2.0 * K * d * d + K * (K + 1.0) * d + 10.0 * (K * (K - 1) / 2) * 18.0 * K + 3.0 * r_ * K * d),
+                                   B * (4.0 * d * d + 24.0 * K * d + 8.0 * K + 16.0 * K * d + 8.0 * r_ + 24.0 * r_ * d
+                                        + 8.0 * K * r_ + 8.0 * K + 20.0)), launch)
+    return r
+
+
 #: widest metric ``metric_solve`` takes: the float64 matrix of a sample lives in LDS (csrc/shoot_step.hip)
 SHOOT_MAX_WIDTH = 128
 

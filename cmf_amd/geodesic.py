@@ -34,8 +34,18 @@ the stars and a float64 solve of the block-arrow normal equations, arm by arm wi
 
     out = geo.mean(xs, weights)                          # xs (B, K, *x_shape): out["mean"] (B, *x_shape) in data space
     out["distances"], out["variance"]                    # (B, K) arm lengths; the estimate of the Frechet variance
+
+``principal`` is the step after the mean: principal geodesic analysis, PCA in the tangent plane at the Frechet mean in
+the pull-back metric.  The arms of the relaxed star give the log vector of every input at the mean, one decode sweep gives G there,
+and one float64 kernel per group (csrc/tangent_pca.hip) diagonalises the weighted covariance in its dual K x K form.
+
+    pga = geo.principal(xs, weights)                     # the values of mean, and beside them
+    pga["variances"], pga["explained"], pga["rank"]      # (B, r) variance per mode and its share; the numerical rank
+    pga["directions"], pga["scores"]                     # (B, r, d) G-orthonormal modes; (B, K, r) coordinates of the inputs
+    walk = geo.principal_paths(pga, component=0)         # walk["path"]: -2 .. +2 standard deviations along the first mode
 """
 import math
+import numbers
 
 import torch
 
@@ -61,7 +71,10 @@ class ManifoldGeodesic:
     ``log`` velocity of one pair of inputs to a third input and shoots along it there.
 
     ``mean`` / ``mean_latents`` find the weighted Frechet mean of K inputs: the loop above with a star of K arms of ``points``
-    latents and one shared free end point as its unit."""
+    latents and one shared free end point as its unit.
+
+    ``principal`` / ``principal_latents`` add the principal modes of variation of the K inputs around that mean (principal geodesic
+    analysis); ``principal_paths`` draws a mode by shooting from the mean in both directions."""
 
     def __init__(self, density, points=17, steps=10, damping=1e-3, up=10.0, down=0.1, shoot_steps=16):
         if int(shoot_steps) < 1:
@@ -221,7 +234,11 @@ class ManifoldGeodesic:
           evaluation (``engine.star_step``).
         Sub-batches of whole stars; enqueues kernels only -- beyond the look at ``weights`` no copy to the
         host, no synchronisation -- and leaves ``head.last_gram`` alone."""
-        prog, P = self.head.program, self.points
+        return self._relax_stars(zs, *self._star_arguments(zs, weights, steps))[0]
+
+    def _star_arguments(self, zs, weights, steps):
+        """The refusals of ``mean_latents`` that need no GPU: (steps, weights as ``_star_weights`` gives them) or a ValueError."""
+        prog = self.head.program
         if not isinstance(zs, torch.Tensor) or zs.dim() != 3 or zs.shape[2] != prog.d or zs.dtype != torch.float32:
             raise ValueError(f"zs must be (B, K, {prog.d}) float32, got {tuple(getattr(zs, 'shape', ()))} "
                              f"{getattr(zs, 'dtype', type(zs).__name__)}")
@@ -230,7 +247,12 @@ class ManifoldGeodesic:
         if B == 0 or steps < 0 or not 1 <= K <= E.STAR_MAX_ARMS:
             raise ValueError(f"mean needs at least one group of 1 <= K <= {E.STAR_MAX_ARMS} inputs and steps >= 0, got {B} groups "
                              f"of {K} and steps = {steps}")
-        weights = self._star_weights(weights, B, K)
+        return steps, self._star_weights(weights, B, K)
+
+    def _relax_stars(self, zs, steps, weights):
+        """``mean_latents`` behind its refusals: (its values, the weights as the kernels saw them: (B, K) float64)."""
+        prog, P = self.head.program, self.points
+        B, K = zs.shape[0], zs.shape[1]
         E.require_gpu(zs, "zs")
         dev = zs.device
         if weights is None:
@@ -243,7 +265,7 @@ class ManifoldGeodesic:
                              f"{prog.tangent_chunk(B * K * P)} samples a decode sweep may hold; use fewer points or fewer inputs")
         with E.scope(self.head.kernels):
             parts = [self._mean(zs[i:i + chunk], w[i:i + chunk].contiguous(), steps) for i in range(0, B, chunk)]
-        return join_parts(parts)
+        return join_parts(parts), w
 
     def _mean(self, zs, w, steps):
         prog, dev, P = self.head.program, zs.device, self.points
@@ -283,6 +305,98 @@ class ManifoldGeodesic:
                 "initial_distances": lengths_0.sum(2), "segment_lengths": lengths, "energy": energy, "initial_energy": energy_0,
                 "variance": energy / w_sum, "gradient": r.grad, "gradient_centre": r.grad_centre,
                 "gradient_max": r.stats[:, 3].contiguous(), "accepted": accepted, "damping": lam, "info": r.info}
+
+    # -- principal geodesic analysis --------------------------------------------------------------
+    @torch.no_grad()
+    def principal(self, xs, weights=None, components=None, steps=None):
+        """Principal geodesic analysis of the K inputs ``xs[b]`` for every b (``xs``, ``weights``, ``steps`` as for ``mean``):
+        ``principal_latents`` of the encoder's latents."""
+        if not isinstance(xs, torch.Tensor) or xs.dim() < 3:
+            raise ValueError(f"xs must be (B, K, *x_shape), got {tuple(getattr(xs, 'shape', ()))}")
+        if xs.shape[0] == 0 or xs.shape[1] == 0:
+            raise ValueError(f"principal needs at least one group of at least one input, got xs {tuple(xs.shape)}")
+        E.require_gpu(xs, "xs")
+        with E.scope(self.head.kernels):
+            z = self.projector.head_input_and_latent(xs.flatten(0, 1))[1]
+        return self.principal_latents(z.view(xs.shape[0], xs.shape[1], -1), weights, components, steps)
+
+    @torch.no_grad()
+    def principal_latents(self, zs, weights=None, components=None, steps=None):
+        """The principal modes of variation of the head's latents ``zs`` (B, K, d) float32 per group b: PCA in the tangent plane at
+        their Frechet mean in the pull-back metric G = J^T J.  ``mean_latents(zs, weights, steps)`` finds the mean; the log vector of
+        input k there is the end difference v_k = N (-3 z_{k,N} + 4 z_{k,N-1} - z_{k,N-2}) / 2 of arm k of the relaxed star, in
+        float64 (it points from the mean towards input k and reaches it in time 1: the mirror image of ``log``'s velocity); G comes
+        from one decode sweep with tangents over the B centres; one kernel (csrc/tangent_pca.hip) diagonalises the weighted
+        covariance sum_k w_k v_k v_k^T G / sum_k w_k in its dual K x K form.  ``components`` = r modes are returned: None means
+        min(K, d), else 1 <= components <= min(K, d).  Returns the values of ``mean_latents``, unchanged, and beside them:
+          ``log_velocities`` (B, K, d) float64; ``metric`` (B, d, d) float32, G at the mean exactly as the kernel read it (its lower
+          triangle); ``variances`` (B, r) float64, descending: the variance along mode j in squared geodesic length;
+          ``directions`` (B, r, d) float64, the modes u_j as latent components, G-orthonormal, largest-magnitude component positive;
+          ``scores`` (B, K, r) float64 = u_j^T G v_k, the coordinate of input k along mode j; ``covectors`` (B, K, d) float64 =
+          G v_k; ``norm2`` (B, K) float64 = v_k^T G v_k, the squared geodesic distance the log vector of arm k claims (compare
+          ``distances``); ``total_variance`` (B,) float64 = sum_k w_k norm2_k / sum_k w_k; ``explained`` (B, r) float64 =
+          variances / total_variance, 0 where that is 0; ``rank`` (B,) int32, the modes whose variance is above d 2^-24 times the
+          largest -- below that a float32 metric leaves it undetermined --: the others have zero directions and scores; ``pga_info``
+          (B,) int32, the code of ``engine.tangent_pca`` (``info`` stays ``mean_latents``').
+        K copies of one input give rank 0 and exact zeros.  Enqueues kernels only -- beyond ``mean_latents``' look at ``weights`` no
+        copy to the host, no synchronisation -- and leaves ``head.last_gram`` alone."""
+        steps, weights = self._star_arguments(zs, weights, steps)
+        prog, N = self.head.program, self.points - 1
+        B, K, d = zs.shape
+        most = min(K, d)
+        r = most if components is None else components
+        if isinstance(r, bool) or not isinstance(r, numbers.Integral) or not 1 <= r <= most:
+            raise ValueError(f"components = {components!r}: need None or an integer 1 <= components <= min(K, d) = {most}")
+        out, w = self._relax_stars(zs, steps, weights)
+        out = dict(out)
+        z = out["latents"].double()
+        logv = ((self.points - 1) * (-3.0 * z[:, :, N] + 4.0 * z[:, :, N - 1] - z[:, :, N - 2]) / 2.0).contiguous()
+        centre = out["mean_latent"]
+        chunk = prog.tangent_chunk(B)
+        with E.scope(self.head.kernels):
+            parts = []
+            for i in range(0, B, chunk):
+                _, T = prog.decode(centre[i:i + chunk], tangents=True)
+                parts.append(E.gram_cholesky(T, d, 1).jtj)
+                del T
+            metric = (parts[0] if len(parts) == 1 else torch.cat(parts)).contiguous()
+            pca = E.tangent_pca(metric, logv, w, r)
+        positive = pca.total > 0
+        explained = torch.where(positive[:, None], pca.variances / torch.where(positive, pca.total, torch.ones_like(pca.total))[:, None],
+                                torch.zeros_like(pca.variances))
+        out.update(log_velocities=logv, metric=metric, variances=pca.variances, directions=pca.directions, scores=pca.scores,
+                   covectors=pca.covectors, norm2=pca.norm2, total_variance=pca.total, explained=explained, rank=pca.rank,
+                   pga_info=pca.info)
+        return out
+
+    @torch.no_grad()
+    def principal_paths(self, result, component=0, extent=2.0, steps=None):
+        """Draw mode ``component`` of a ``principal`` / ``principal_latents`` result: the geodesics that leave the mean with the
+        latent velocities -/+ ``extent`` sqrt(lambda_j) u_j, ``extent`` standard deviations along the mode in each direction, by one
+        ``shoot_latents`` call of 2 B trajectories of S = ``steps`` (default ``shoot_steps``) steps.  Returns device tensors:
+          ``path``, ``path_head`` and ``latents`` (B, 2 S + 1, ...): the two halves joined through the mean, running from -extent
+          (node 0) through the mean (node S) to +extent (node 2 S); ``speed2`` (B, 2, S + 1) and ``info`` (B, 2) of ``shoot_latents``,
+          [:, 0] the negative half and [:, 1] the positive one, each from the mean outwards.
+        A group whose rank is <= ``component`` has zero velocity and stays at the mean."""
+        need = ("mean_latent", "mean_head", "mean", "variances", "directions")
+        if not isinstance(result, dict) or any(key not in result for key in need):
+            raise ValueError("result must be what principal / principal_latents returned")
+        lam, u, z0 = result["variances"], result["directions"], result["mean_latent"]
+        j, extent = int(component), float(extent)
+        if not 0 <= j < lam.shape[1]:
+            raise ValueError(f"component = {component}: the result holds the components 0 .. {lam.shape[1] - 1}")
+        if not (math.isfinite(extent) and extent > 0):
+            raise ValueError(f"principal_paths needs a finite extent > 0, got {extent}")
+        B = z0.shape[0]
+        v = (extent * lam[:, j].clamp_min(0.0).sqrt())[:, None] * u[:, j]                  # zero beyond the rank: u_j is
+        shot = self.shoot_latents(torch.cat([z0, z0]), torch.cat([-v, v]), steps)
+        S = shot["latents"].shape[1] - 1
+        halves = lambda t: t.view(2, B, *t.shape[1:])
+        # the middle node is the result's own mean (the shot's node 0 decodes the same latent on another path)
+        join = lambda t, mean: torch.cat([halves(t)[0][:, 1:].flip(1), mean[:, None], halves(t)[1][:, 1:]], 1)
+        return {"path": join(shot["path"], result["mean"]), "path_head": join(shot["path_head"], result["mean_head"]),
+                "latents": join(shot["latents"], z0),
+                "speed2": halves(shot["speed2"]).transpose(0, 1).contiguous(), "info": halves(shot["info"]).transpose(0, 1).contiguous()}
 
     # -- the exponential map (DESIGN 4.3h) -----------------------------------------------------------------
     @torch.no_grad()

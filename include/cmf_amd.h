@@ -562,6 +562,30 @@ int cmf_star_step(const float* t, long long t_b, long long t_r, int n_rows, int 
                   long long first, const float* jtj, const float* cross, const float* xhat, const double* weights,
                   const double* damping, double* grad, double* grad_centre, double* delta, double* delta_centre, double* arm_stats,
                   double* seg2, int* info, double* ws, long long ws_doubles, void* stream);
+/* Principal geodesic analysis of groups of `arms` = K tangent vectors at one point each: PCA in the tangent plane in the
+ * pull-back metric G = J^T J, in its dual (K x K) form, per group in float64 (no contraction), one workgroup per group.
+ *   jtj [B][d][d] float32: the Gram matrix as ONE cmf_gram_cholesky attempt leaves it; only the lower triangle i >= j is read,
+ *     nothing is written.  vectors [B][K][d] float64: the latent components v_k.  weights [B][K] float64, finite and > 0.
+ * With W = sum_k w_k (arm order), y_k = G v_k (j ascending) and q_kl = sum_i y_k[i] v_l[i] (i ascending):
+ *   M_kl = M_lk = ((sqrt(w_k) sqrt(w_l)) q_kl) / W for l <= k;  M = P Lambda P^T by the cyclic Jacobi method of cmf_gram_spectrum
+ *   (the same ordering, rotation rule and stop, CMF_SPECTRUM_MAX_SWEEPS);  lambda descending (equal values in descending order of
+ *   their position on the converged diagonal);  rank = #{ j : lambda_j > (d 2^-24) lambda_1 }.
+ *   variances [B][r] float64, r = `components`: lambda_0 .. lambda_{r-1}, as computed (zero and negative values included).
+ *   directions [B][r][d] float64: for j < rank u_j = (sum_k (sqrt(w_k) p_kj) v_k) / sqrt(W lambda_j), k ascending: G-orthonormal;
+ *     the component of largest magnitude is positive (lowest index on ties).  For j >= rank: 0.  The slice of a group is also its
+ *     workgroup's working storage during the launch, like covectors.
+ *   scores [B][K][r] float64: for j < rank (sqrt(W lambda_j) p_kj) / sqrt(w_k) = u_j^T G v_k, with the sign of u_j.  Else 0.
+ *   covectors [B][K][d] float64 = y_k;  norm2 [B][K] float64 = q_kk = v_k^T G v_k;  total [B] float64 = (sum_k w_k q_kk) / W.
+ *   rank, sweeps [B] int32 (sweeps: those executed, the final rotation-free one included);
+ *   info [B] int32: 0 ok; 1 sweep cap reached; 2 a non-finite value in the lower triangle of jtj or in vectors, or a weight that is
+ *     not finite and > 0 (every float64 output of the group is NaN, rank and sweeps 0).  Other groups are unaffected.
+ * A group's outputs are a function of its own inputs and of (d, K, r) alone: no atomics, independent of B, of the group's position
+ * and of completion order, and they repeat bit for bit.
+ * 1 <= d <= 128, 1 <= arms <= 64, 1 <= components <= arms, B >= 1, no pointer NULL, float64 pointers 8-byte aligned, the others
+ * 4-byte.  Anything else: CMF_EINVAL, nothing is written.  No allocation, no synchronisation.                                   */
+int cmf_tangent_pca(const float* jtj, const double* vectors, const double* weights, int d, int arms, int components, int B,
+                    double* variances, double* directions, double* scores, double* covectors, double* norm2, double* total,
+                    int* rank, int* sweeps, int* info, void* stream);
 /* Reverse of the head above for training (autograd through non_square.py:307-308, :280-294, :87-100):
  *   dt(b, r, :) = 2 * t(b, r, :) * (g_logdet[b] * jtj_b^-1 + g_l1off[b] * sign(jtj_b)[i != j]
  *                                   + g_l1diag[b] * sign(jtj_b)[i == j])
