@@ -5,6 +5,7 @@ Public surface mirrors the reference for this path:
     density = get_density(get_schema(get_config("mnist", latent_dimension=64)), x_train).cuda().eval()
     density.elbo(x, add_reconstruction=True, add_offdiagonal_metric_reg=True)["elbo"]      # (B, 1)
 """
+from .curvature import ManifoldCurvature
 from .densities import PrecisionGuard
 from .factory import get_density
 from .geodesic import ManifoldGeodesic
@@ -16,4 +17,4 @@ from .schemas import DATA_SHAPES, get_config, get_schema
 
 __all__ = ["get_density", "get_config", "get_schema", "DATA_SHAPES", "get_non_square_train_metrics",
            "get_non_square_parameters", "PrecisionGuard", "MetricStatistics", "MetricSpectrum", "effective_rank",
-           "ManifoldProjector", "ManifoldGeodesic"]
+           "ManifoldProjector", "ManifoldGeodesic", "ManifoldCurvature"]

@@ -118,6 +118,7 @@ SIGNATURES = {
     "cmf_star_step": (_i, [_fp, _ll, _ll, _i, _i, _i, _i, _i, _i, _ll, _fp, _fp, _fp, _fp, _fp, _fp, _fp, _fp, _fp, _fp, _fp, _fp, _fp,
                            _ll, _fp]),
     "cmf_tangent_pca": (_i, [_fp, _fp, _fp, _i, _i, _i, _i, _fp, _fp, _fp, _fp, _fp, _fp, _fp, _fp, _fp, _fp]),
+    "cmf_second_form": (_i, [_fp, _ll, _ll, _i, _i, _i, _i, _i, _fp, _fp, _ll, _ll, _fp, _fp, _fp, _fp, _fp, _fp, _fp, _fp]),
     "cmf_stanh_backward": (_i, [_fp, _fp, _fp, _fp, _fp, _fp, _fp, _fp, _fp, _i, _i, _i, _fp]),
     "cmf_tanh_cross_terms": (_i, [_fp, _ll, _ll, _fp, _ll, _ll, _fp, _fp, _i, _i, _i, _fp]),
     "cmf_tanh_backward": (_i, [_fp, _fp, _fp, _ll, _fp, _fp]),

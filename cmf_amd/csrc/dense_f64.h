@@ -1,10 +1,10 @@
 // The float64 linear algebra that the per-sample / per-curve manifold kernels share: gn_step.hip, curve_step.hip,
-// shoot_step.hip, transport_step.hip and star_step.hip.  Every piece is for one workgroup of F64_NT = 256 threads, all of which call it
-// (the barriers inside are unconditional), and is inlined into its caller.
+// shoot_step.hip, transport_step.hip, star_step.hip and second_form.hip.  Every piece is for one workgroup of F64_NT = 256 threads, all of
+// which call it (the barriers inside are unconditional), and is inlined into its caller.
 //
 // Contraction: this header carries no fp-contract pragma; the helpers take the state in force where the header is INCLUDED.
-// curve_step.hip, transport_step.hip and star_step.hip include it after their `#pragma clang fp contract(off)` (one rounded operation per
-// multiply and add); gn_step.hip and shoot_step.hip have no pragma and fuse multiply-adds.  Moving an #include across a pragma,
+// curve_step.hip, transport_step.hip, star_step.hip and second_form.hip include it after their `#pragma clang fp contract(off)` (one
+// rounded operation per multiply and add); gn_step.hip and shoot_step.hip have no pragma and fuse multiply-adds.  Moving an #include across a pragma,
 // or adding a pragma here, changes output bits.
 #pragma once
 #include "common.h"

@@ -1438,6 +1438,73 @@ def transport_chain(jtj, cross, w0, points):
     return r
 
 
+#: widest Jacobian ``second_form`` takes, and the directions of one frame: the float64 window of a sample -- the metric and the
+#: m (m + 1) / 2 right-hand sides -- lives in LDS (csrc/second_form.hip)
+CURVATURE_MAX_WIDTH = 128
+CURVATURE_MAX_FRAME = 4
+
+
+class SecondFormResult:
+    """Outputs of ``second_form`` (all on the device, float64 unless noted) for B samples, frames of m directions and q = m (m + 1) / 2
+    pairs (a, b), a <= b, a-major: ``second_gram`` (B, q, q), the Gram matrix of the normal components II_ab, whole; ``christoffel``
+    (B, q, d) = G^-1 J^T H_ab; ``frame_metric`` (B, m, m) = u_a^T G u_b; ``stats`` (B, 4) = [sum_{a<b} ||D_ab - D_ba||^2,
+    sum_{a<b} ||H_ab||^2, trace H^T H, trace second_gram]; ``info`` (B,) int32 (0 ok; 1 non-positive pivot of G: second_gram,
+    christoffel, stats[:, 3] NaN; 2 non-finite input or a step that is not finite and > 0: everything NaN)."""
+    __slots__ = ("second_gram", "christoffel", "frame_metric", "stats", "info")
+
+
+def second_form(T, jtj, S, frame, step):
+    """The per-sample float64 reduction of the curvature estimate: from the Jacobian stack ``T`` of a decode sweep at B
+    latents, its Gram matrix ``jtj`` (B, d, d) float32 (one ``gram_cholesky`` attempt; the lower triangles are read), ``frame``
+    (B, m, d) float64 -- m <= min(d, 4) unit latent directions per sample --, ``step`` (B,) float64 > 0 and the 16-column sweep ``S``
+    over the 2 m B shifted latents (sample (b m + a) 2 + sign at z_b +- step_b frame[b, a], column c < m = J frame[b, c]): the
+    symmetrised central differences H_ab, the Gram matrix of their normal components (a Schur complement), the Christoffel
+    contractions G^-1 J^T H_ab and the metric of the frame.  Returns a ``SecondFormResult``.  Deterministic per sample; one launch, no
+    synchronisation."""
+    _check_tangent(T)
+    if not isinstance(S, Tangent):
+        raise ValueError(f"S must be an engine.Tangent, got {type(S).__name__}")
+    B, d = _gram_stack(jtj, "B", "the second-form kernel supports", CURVATURE_MAX_WIDTH)
+    dev = jtj.device
+    _check_tensor("frame", frame, torch.float64, f"({B}, m, {d})", lambda t: t.dim() == 3 and t.shape[0] == B and t.shape[2] == d, dev)
+    m = frame.shape[1]
+    if not 1 <= m <= min(d, CURVATURE_MAX_FRAME):
+        raise ValueError(f"m = {m}: the second-form kernel takes frames of 1 <= m <= min(d, {CURVATURE_MAX_FRAME}) = "
+                         f"{min(d, CURVATURE_MAX_FRAME)} directions")
+    _check_tensor("step", step, torch.float64, f"({B},)", lambda t: t.shape == (B,), dev)
+    if T.B != B or T.nc % 16 or T.nc < d or T.N < 1 or T.data.device != dev:
+        raise ValueError(f"T (B = {T.B}, N = {T.N}, nc = {T.nc}) on {T.data.device} must hold d = {d} <= nc columns, nc % 16 == 0, for "
+                         f"the {B} samples of jtj on {dev}")
+    if S.B != 2 * m * B or S.N != T.N or S.nc != 16 or S.nc < m or S.data.device != dev:
+        raise ValueError(f"S (B = {S.B}, N = {S.N}, nc = {S.nc}) on {S.data.device} must hold the 2 m B = {2 * m * B} shifted samples "
+                         f"of {T.N} elements in 16 >= m = {m} columns on {dev}")
+    q = m * (m + 1) // 2
+    r = SecondFormResult()
+    r.second_gram = torch.empty(B, q, q, dtype=torch.float64, device=dev)
+    r.christoffel = torch.empty(B, q, d, dtype=torch.float64, device=dev)
+    r.frame_metric = torch.empty(B, m, m, dtype=torch.float64, device=dev)
+    r.stats = torch.empty(B, 4, dtype=torch.float64, device=dev)
+    r.info = torch.empty(B, dtype=torch.int32, device=dev)
+    if B == 0:
+        return r
+    n = T.N
+    launch = lambda: _lib.check(_lib.load().cmf_second_form(_p(T.data), T.t_b, T.t_r, n, T.nc, d, m, B, _p(jtj), _p(S.data), S.t_b,
+                                                            S.t_r, _p(frame), _p(step), _p(r.second_gram), _p(r.christoffel),
+                                                            _p(r.frame_metric), _p(r.stats), _p(r.info), _stream()), "cmf_second_form")
+
+    def cost():
+        # float64: the differences 3 m^2 D, J^T H 2 D d q, H^T H and the two asymmetry sums 2 D (q (q + 1) / 2 + m (m - 1)), the
+        # elimination d^3 / 3 with its q rows q d^2, the Schur complement 3 d q (q + 1) / 2, the back substitution q d^2, the frame's
+        # metric 2 m d^2; bytes: the live quarter-rows of J, the first quarter-rows of S twice (L2 the second time), the triangle of G,
+        # the frame, the outputs
+        ncl = min(T.nc, -(-d // 4) * 4)
+        return (B * (3.0 * m * m * n + 2.0 * n * d * q + 2.0 * n * (q * (q + 1) / 2 + m * (m - 1)) + d ** 3 / 3.0 + 2.0 * q * d * d
+                     + 1.5 * d * q * (q + 1) + 2.0 * m * d * d),
+                B * (4.0 * n * ncl + 2 * 16.0 * n * 2 * m + 2.0 * d * (d + 1) + 8.0 * m * d + 8.0 * (q * q + q * d + m * m + 5) + 4.0))
+    _timed("second_form", cost, launch)
+    return r
+
+
 def gram_backward(T, jtj, g_logdet=None, g_l1off=None, g_l1diag=None):
     """Cotangent of the Jacobian stack T for a loss with d/d logdet = g_logdet, d/d l1_off = g_l1off, d/d l1_diag =
     g_l1diag (each (B,) or None): what autograd yields through non_square.py:307-308, :280-294, :87-100."""

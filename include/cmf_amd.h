@@ -586,6 +586,34 @@ int cmf_star_step(const float* t, long long t_b, long long t_r, int n_rows, int 
 int cmf_tangent_pca(const float* jtj, const double* vectors, const double* weights, int d, int arms, int components, int B,
                     double* variances, double* directions, double* scores, double* covectors, double* norm2, double* total,
                     int* rank, int* sweeps, int* info, void* stream);
+/* The second fundamental form of the manifold in a latent frame: per sample, in float64 (no contraction), from the centre
+ * sweep's Jacobian stack, its metric, a frame of m unit latent directions u_0 .. u_{m-1}, the step h and a sweep at the 2 m shifted
+ * latents z +- h u_a.  q = m (m + 1) / 2 pairs p = (a, b), a <= b, in a-major order.
+ *   t, t_b, t_r, n_rows, nc: the centre stack as cmf_gram_cholesky takes it (both layouts through the two strides); columns d .. nc - 1
+ *     are padding whose contents influence no output.
+ *   jtj [B][d][d] float32: the Gram matrix as ONE cmf_gram_cholesky attempt leaves it; only the lower triangle i >= j is read,
+ *     nothing is written.
+ *   s, s_b, s_r: the shifted stack of 2 m B samples of n_rows rows and 16 columns; sample (b m + a) 2 + sign (sign 0: + h u_a, 1:
+ *     - h u_a) begins at s + ((b m + a) 2 + sign) s_b, its row r at + r s_r; column c < m holds J(z_b +- h u_a) u_c, columns m .. 15 are
+ *     padding whose contents influence no output.
+ *   frame [B][m][d] float64;  step [B] float64, h > 0.
+ * With delta_ab[r] = s(+a)[r][b] - s(-a)[r][b], D_ab = delta_ab / (2 h), H_p = (delta_ab + delta_ba) / (4 h), A = J^T H, S2 = H^T H:
+ *   second_gram [B][q][q] = S2 - A^T G^-1 A, whole and mirrored: the Gram matrix of the normal components of the H_p;
+ *   christoffel [B][q][d] = G^-1 A_p;  frame_metric [B][m][m] = u_a^T G u_b (j, then r ascending; the lower triangle mirrored);
+ *   stats [B][4] = { sum_{a<b} ||D_ab - D_ba||^2, sum_{a<b} ||H_ab||^2, trace S2, trace second_gram };
+ *   info [B] int32: 0 ok; 1 a pivot of G was not positive and finite (second_gram, christoffel and stats[3] are NaN, the rest is
+ *     valid); 2 a non-finite value in the first d columns of t, the first m columns of s, the lower triangle of jtj or in frame, or a
+ *     step that is not finite and > 0 (every float64 output of the sample is NaN; found before anything is written: takes precedence
+ *     over 1).  Other samples are unaffected.
+ * The sums over the rows run over the raw differences; each folded sum is divided once by 4 h, (4 h)^2 or (2 h)^2.
+ * A sample's outputs are a function of its own inputs and of (n_rows, nc, d, m) alone: no atomics, independent of B, of its position
+ * in the batch and of completion order, and they repeat bit for bit.
+ * 1 <= d <= 128, 1 <= m <= min(d, 4), nc % 16 == 0, d <= nc, t_b and t_r >= nc, s_b and s_r >= 16, all four % 4 == 0, t and s 16-byte
+ * aligned, float64 pointers 8-byte aligned, the others 4-byte, no pointer NULL, n_rows, B >= 1.  Anything else: CMF_EINVAL, nothing is
+ * written.  No allocation, no synchronisation.                                                                                       */
+int cmf_second_form(const float* t, long long t_b, long long t_r, int n_rows, int nc, int d, int m, int B, const float* jtj,
+                    const float* s, long long s_b, long long s_r, const double* frame, const double* step, double* second_gram,
+                    double* christoffel, double* frame_metric, double* stats, int* info, void* stream);
 /* Reverse of the head above for training (autograd through non_square.py:307-308, :280-294, :87-100):
  *   dt(b, r, :) = 2 * t(b, r, :) * (g_logdet[b] * jtj_b^-1 + g_l1off[b] * sign(jtj_b)[i != j]
  *                                   + g_l1diag[b] * sign(jtj_b)[i == j])
