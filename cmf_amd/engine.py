@@ -1074,6 +1074,82 @@ def gauss_newton_step(T, jtj, x, xhat, damping):
     return r
 
 
+class WeightedGaussNewtonResult(GaussNewtonResult):
+    """Outputs of ``weighted_gauss_newton_step``: the fields of ``GaussNewtonResult`` for the weighted system -- ``grad`` = J^T (w o
+    (x - x_hat)), ``delta`` = (G_w + lambda diag G_w)^-1 grad, ``stats`` = [sum w r^2, grad^T delta, delta^T G_w delta, max |grad_k|]
+    -- plus ``gram`` (B, d, d) float32 = G_w = J^T diag(w) J, symmetric bit for bit.  ``info``: 0 ok, 1 non-positive pivot (delta and
+    stats[:, 1:3] NaN), 2 a negative or non-finite weight or a non-finite value in a row with w > 0 (everything NaN)."""
+    __slots__ = ("gram",)
+
+
+def _weighted_triple(w, x, xhat):
+    """The checks ``weighted_gauss_newton_step`` and ``weighted_residual_sqnorm`` share; returns (B, elements per sample)."""
+    B, n = _residual_pair(x, xhat)
+    _check_tensor("w", w, torch.float32, f"({B}, ...) of {n} elements per sample", lambda t: t.dim() >= 2 and t.shape[0] == B and
+                  t.numel() == B * n, x.device)
+    return B, n
+
+
+def weighted_residual_sqnorm(w, x, xhat):
+    """sum_i w_bi (x_bi - xhat_bi)^2 per sample in float64, by the cost-only mode of the weighted Gauss-Newton step kernel (the
+    same arithmetic, bit for bit, as ``weighted_gauss_newton_step(...).stats[:, 0]``); elements with w == 0 are not read.  Returns
+    ((B,) float64, info (B,) int32 -- 0, or 2 with a NaN cost for a negative or non-finite weight or a non-finite value where
+    w > 0).  One launch, no synchronisation."""
+    B, n = _weighted_triple(w, x, xhat)
+    stats = torch.empty(B, 4, dtype=torch.float64, device=x.device)
+    info = torch.empty(B, dtype=torch.int32, device=x.device)
+    if B == 0:
+        return stats[:, 0], info
+    launch = lambda: _lib.check(_lib.load().cmf_weighted_gauss_newton_step(
+        None, 0, 0, n, 0, 0, B, _p(w), _p(x), _p(xhat), None, None, None, None, _p(stats), _p(info), _stream()),
+        "cmf_weighted_gauss_newton_step")
+
+    def cost():
+        live = float((w > 0).sum())                                   # a host look: under a timer only
+        return 4.0 * live, 4.0 * B * n + 8.0 * live + 12.0 * B
+    _timed("weighted_residual_sqnorm", cost, launch)
+    return stats[:, 0], info
+
+
+def weighted_gauss_newton_step(T, w, x, xhat, damping, d=None):
+    """One damped, weighted Gauss-Newton step per sample: from the Jacobian stack ``T`` of a decode sweep, of which
+    the first ``d`` columns are J (default: all ``T.nc``; there is no Gram matrix among the arguments to tell the width), the
+    weights ``w`` >= 0, the head-space input ``x`` and the reconstruction ``xhat`` (B, ...) float32 and ``damping`` (B,) float64
+    >= 0: gram = J^T diag(w) J in float32 and, in float64, grad = J^T (w o (x - xhat)) and delta = (gram + damping diag gram)^-1
+    grad -- J is read once, and only its rows with w > 0.  Returns a ``WeightedGaussNewtonResult``.  Deterministic per sample;
+    one launch, no synchronisation."""
+    _check_tangent(T)
+    B, n = _weighted_triple(w, x, xhat)
+    dev = x.device
+    d = T.nc if d is None else int(d)
+    _check_width(d, "the weighted Gauss-Newton step kernel supports", PROJECT_MAX_WIDTH)
+    if T.B != B or T.N != n or T.nc % 16 or T.nc < d or T.data.device != dev:
+        raise ValueError(f"T (B = {T.B}, N = {T.N}, nc = {T.nc}) on {T.data.device} must hold d = {d} <= nc columns, nc % 16 == 0, "
+                         f"for the {B} samples of {n} elements of x on {dev}")
+    _check_damping(damping, B, dev)
+    r = WeightedGaussNewtonResult()
+    r.gram = torch.empty(B, d, d, dtype=torch.float32, device=dev)
+    r.grad = torch.empty(B, d, dtype=torch.float64, device=dev)
+    r.delta = torch.empty(B, d, dtype=torch.float64, device=dev)
+    r.stats = torch.empty(B, 4, dtype=torch.float64, device=dev)
+    r.info = torch.empty(B, dtype=torch.int32, device=dev)
+    if B == 0:
+        return r
+    launch = lambda: _lib.check(_lib.load().cmf_weighted_gauss_newton_step(
+        _p(T.data), T.t_b, T.t_r, n, T.nc, d, B, _p(w), _p(x), _p(xhat), _p(damping), _p(r.gram), _p(r.grad), _p(r.delta),
+        _p(r.stats), _p(r.info), _stream()), "cmf_weighted_gauss_newton_step")
+
+    def cost():
+        # per live row: the lower tile triangle of the Gram MFMAs (2 flop per product, nt (nt + 1) / 2 tiles of 256), the float64
+        # J^T (w r) 2 d and the cost 4; per sample the elimination as in gauss_newton_step.  Bytes: w once; per live row x, xhat
+        # and the 16-column tiles of J that hold the first d columns ONCE; gram out and its triangle back twice, the outputs
+        live = float((w > 0).sum())                                   # a host look: under a timer only
+        nt = -(-d // 16)
+        return (live * (2.0 * 256.0 * nt * (nt + 1) / 2 + 2.0 * d + 4.0) + B * (d ** 3 / 3.0 + 3.5 * d * d + 2.0 * d),
+                4.0 * B * n + live * (8.0 + 64.0 * nt) + B * (4.0 * d * d + 4.0 * d * (d + 1) + 16.0 * d + 44.0))
+    _timed("weighted_gauss_newton_step", cost, launch)
+    return r
+
 #: widest Jacobian ``cross_gram`` / ``curve_step`` take (csrc/curve_step.hip: the elimination window of a curve lives in LDS up to
 #: d = 64 and in a workspace slice up to d = 128)
 GEODESIC_MAX_WIDTH = 128

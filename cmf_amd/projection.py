@@ -13,6 +13,7 @@ started at the encoder's latent.  A step is one decode sweep (x_hat, J), the Gra
 import torch
 
 from . import engine as E
+from .bijections import AffineBijection, Squeeze2dBijection, ViewBijection, _Elementwise
 from .densities import BijectionDensity, DataParallelDensity, WrapperDensity
 from .metric_stats import metric_head
 
@@ -43,6 +44,25 @@ def to_data_space(chain, x):
     for bijection in reversed(chain):
         x = bijection.z_to_x(x)["x"]
     return x
+
+
+def to_head_space_weights(chain, w):
+    """The per-element weights ``w`` (B, *data shape) mapped to the head's input space through the bijections ``chain``
+    (``wrapper_bijections``): an elementwise bijection (logit, scalar multiplication / addition, affine) moves every element on its
+    own and leaves the weights as they are -- the same tensor --, a reshaping one (``ViewBijection``, ``Squeeze2dBijection``)
+    permutes them with the index map its own ``x_to_z`` applies to data.  Anything else: NotImplementedError."""
+    for bijection in chain:
+        if isinstance(bijection, (_Elementwise, AffineBijection)):
+            continue
+        if isinstance(bijection, ViewBijection):
+            w = w.reshape(w.shape[0], *bijection.z_shape)
+        elif isinstance(bijection, Squeeze2dBijection):
+            x2z = bijection._maps.get("x2z", w.device).long()        # z[r] = x[x2z[r]]
+            w = w.reshape(w.shape[0], -1).index_select(1, x2z).view(w.shape[0], *bijection.z_shape)
+        else:
+            raise NotImplementedError(f"weights cannot be carried through a {type(bijection).__name__} in front of the head: it "
+                                      "mixes elements (only elementwise and reshaping bijections are built)")
+    return w
 
 
 def join_parts(parts):
@@ -149,3 +169,76 @@ class ManifoldProjector:
         return {"latent": z, "reconstruction_head": x_hat, "reconstruction": to_data_space(self.chain, x_hat), "distance2": d2,
                 "initial_distance2": d2_0, "tangential2": r.stats[:, 1].contiguous(), "gradient": r.grad, "accepted": accepted,
                 "damping": lam, "info": r.info}
+
+    def evaluate_weighted(self, w, y, z, lam):
+        """Decode with tangents at ``z`` and the weighted step kernel: the ``engine.WeightedGaussNewtonResult``."""
+        prog = self.head.program
+        x_hat, T = prog.decode(z, tangents=True)
+        return E.weighted_gauss_newton_step(T, w, y, x_hat.contiguous(), lam, d=prog.d)
+
+    @torch.no_grad()
+    def complete(self, x, weights, steps=None, init=None):
+        """Weighted projection: minimise sum_i w_i (y_i - g(z)_i)^2 over z for every sample -- the projection of an
+        input with missing (w_i = 0) or unevenly trusted elements; g(z) at the elements with w_i = 0 is the imputation.
+          ``x``: as for ``project``, finite everywhere; its values where the weight is zero only choose the starting latent (the
+          encoder needs every element).  ``weights``: x's shape, or broadcastable over the batch ((*x.shape[1:]) or (1,
+          *x.shape[1:])); floating point or bool, on x's device, >= 0.  They are carried to the head's input space through the
+          wrapper chain (``to_head_space_weights``), where the cost is measured -- as ``distance2`` is.  ``init``: optional (B, d)
+          float32 starting latent instead of the encoder's.
+        The loop is ``project``'s -- the same dampings, clamps and strict ``<`` acceptance, on the weighted cost, with a closing
+        evaluation at lambda = 0 -- and so are the returned keys, except: ``cost`` and ``initial_cost`` (B,) float64 in place of the
+        distances; ``tangential2`` and ``gradient`` from the weighted system; ``distance2``, the unweighted ||y - g(z)||^2 over ALL
+        elements, as a diagnostic; ``observed`` (B,) int32, the elements with w > 0.
+        Whether a weight is negative or not finite is the kernel's finding, not a host look: such a sample never accepts a step
+        and closes with ``info`` = 2 and NaN costs.  The iteration converges from the encoder's latent of a mildly wrong input with
+        clearly more observed elements than 2 d; from a harsher start -- another sample's values in the hidden elements, or fewer
+        observed elements than about 2 d -- samples can end in a local minimum or on a singular weighted Gram matrix (``info`` = 1).
+        Sub-batches like ``project``; enqueues kernels only, and leaves ``head.last_gram`` alone."""
+        steps = self.steps if steps is None else int(steps)
+        prog, B = self.head.program, x.shape[0]
+        if B == 0 or steps < 0:
+            raise ValueError(f"complete needs at least one sample and steps >= 0, got {B} samples and steps = {steps}")
+        if not isinstance(weights, torch.Tensor) or not (weights.is_floating_point() or weights.dtype == torch.bool):
+            raise ValueError(f"weights must be a floating point or bool tensor, got {getattr(weights, 'dtype', type(weights).__name__)}")
+        if tuple(weights.shape) not in (tuple(x.shape), tuple(x.shape[1:]), (1, *x.shape[1:])):
+            raise ValueError(f"weights must have x's shape {tuple(x.shape)} or broadcast over its batch, got {tuple(weights.shape)}")
+        if init is not None and (not isinstance(init, torch.Tensor) or init.dtype != torch.float32 or tuple(init.shape) != (B, prog.d)):
+            raise ValueError(f"init must be a float32 ({B}, {prog.d}) tensor, got {getattr(init, 'dtype', type(init).__name__)} "
+                             f"{tuple(getattr(init, 'shape', ()))}")
+        to_head_space_weights(self.chain, torch.empty(1, *x.shape[1:]))                # refuses what cannot be mapped, before any launch
+        for name, v in (("weights", weights), ("init", init)):
+            if v is not None and v.device != x.device:
+                raise ValueError(f"{name} must be on x's device {x.device}, got {v.device} (there is no CPU fallback)")
+        E.require_gpu(x)
+        w = weights.to(torch.float32).expand(x.shape)
+        chunk = prog.tangent_chunk(B)
+        with E.scope(self.head.kernels):
+            parts = [self._complete(x[i:i + chunk], w[i:i + chunk], steps, None if init is None else init[i:i + chunk])
+                     for i in range(0, B, chunk)]
+        return join_parts(parts)
+
+    def _complete(self, x, w, steps, init):
+        prog = self.head.program
+        y, z = self.head_input_and_latent(x)
+        if init is not None:
+            z = init.contiguous().clone()
+        w = to_head_space_weights(self.chain, w).reshape(y.shape).contiguous()
+
+        def at(z):                                                    # the state of ``lm_loop``: (z, g(z), sum w (y - g(z))^2)
+            x_hat = prog.decode(z, tangents=False)[0].contiguous()
+            return z, x_hat, E.weighted_residual_sqnorm(w, y, x_hat)[0]
+
+        def trial(state, lam):
+            r = self.evaluate_weighted(w, y, state[0], lam)
+            solved = r.info == 0
+            return solved, at(state[0] + torch.where(solved[:, None], r.delta, torch.zeros_like(r.delta)).float())
+
+        state = at(z)
+        c_0 = state[2].clone()
+        lam = torch.full((x.shape[0],), self.damping, dtype=torch.float64, device=x.device)
+        (z, x_hat, c), lam, accepted = lm_loop(state, 2, lam, steps, self.up, self.down, trial)
+        r = self.evaluate_weighted(w, y, z, torch.zeros_like(lam))
+        return {"latent": z, "reconstruction_head": x_hat, "reconstruction": to_data_space(self.chain, x_hat), "cost": c,
+                "initial_cost": c_0, "tangential2": r.stats[:, 1].contiguous(), "gradient": r.grad,
+                "distance2": E.residual_sqnorm(y, x_hat)[0], "observed": (w > 0).flatten(1).sum(1).to(torch.int32),
+                "accepted": accepted, "damping": lam, "info": r.info}

@@ -459,6 +459,28 @@ int cmf_gram_spectrum(const float* jtj, int d, int B, double* eigenvalues, doubl
 int cmf_gauss_newton_step(const float* t, long long t_b, long long t_r, int n_rows, int nc, int d, int B,
                           const float* jtj, const float* x, const float* xhat, const double* damping,
                           double* grad, double* delta, double* stats, int* info, void* stream);
+/* One damped, weighted Gauss-Newton step per sample: the projection with missing or unevenly trusted elements,
+ *   min_z sum_i w_i (x_i - g(z)_i)^2.  In one pass over the rows of J with w_i > 0:
+ *   G_w = J^T diag(w) J (float32 MFMA accumulation; the operand w_i J_ik is rounded to float32),  r = x - xhat,
+ *   g_w = J^T (w o r) and cost = sum_i w_i r_i^2 in float64;  then  A = G_w + damping[b] diag(G_w),  delta = A^-1 g_w  in float64
+ *   on the float32 matrix written to gram (Cholesky of A in LDS, pivots only: the elimination of cmf_gauss_newton_step).
+ *   t, t_b, t_r, n_rows, nc, x, xhat, damping: as for cmf_gauss_newton_step.  w [B][n_rows] float32, contiguous, >= 0.
+ *   A row with w == 0 is never read -- x, xhat and row i of t may hold anything there, NaN included, and reach no output.
+ *   gram [B][d][d] float32 = G_w, symmetric bit for bit (the lower tile triangle is computed, the rest mirrored);
+ *   grad [B][d], delta [B][d] float64;  stats [B][4] float64 = { cost, g^T delta, delta^T G_w delta, max_k |g_k| };
+ *   info [B] int32: 0 ok; 1 a pivot of A was not positive and finite (delta, stats[1], stats[2] are NaN; gram, grad, stats[0],
+ *     stats[3] are valid): fewer rows with w > 0 than d at damping 0, or no such row at all; 2 a weight that is negative or not
+ *     finite, or a non-finite value in a row with w > 0 of x, xhat or the first d columns of t (every output is NaN).
+ * Cost-only mode, t == NULL: only stats[b][0] and info[b] (0 or 2) are written -- the same bits as the full mode gives; t_b, t_r,
+ *   nc, d are ignored and damping, gram, grad, delta may be NULL.
+ * A sample's outputs are a function of its own inputs and of (n_rows, d) alone, the summation order of (n_rows, d) and of the
+ * positions of the rows with w > 0: no atomics, independent of B, of the sample's position in the batch and of the order in which
+ * workgroups finish, and they repeat bit for bit.
+ * With t: 1 <= d <= 128, nc % 16 == 0, d <= nc, t_b and t_r >= nc and % 4 == 0, t 16-byte aligned; always: n_rows, B >= 1,
+ * float64 pointers 8-byte aligned.  Anything else: CMF_EINVAL.  No allocation, no synchronisation.                             */
+int cmf_weighted_gauss_newton_step(const float* t, long long t_b, long long t_r, int n_rows, int nc, int d, int B,
+                                   const float* w, const float* x, const float* xhat, const double* damping, float* gram,
+                                   double* grad, double* delta, double* stats, int* info, void* stream);
 /* One damped Gauss-Newton step on whole discretised curves with fixed end points.  A curve has `points` = P >= 3
  * points, N = P - 1 segments and M = P - 2 interior points; samples are curve-major: point i of curve c is sample c P + i of the
  * Jacobian stack t, of jtj and of xhat.  With r_i = xhat_{i+1} - xhat_i:
