@@ -18,6 +18,19 @@ int cmf_device_cus();
 
 static inline int cmf_ceil_div(long long a, long long b) { return (int)((a + b - 1) / b); }
 
+// A launch gets 48 KiB of dynamic LDS without asking: above that, kernel k's attribute is raised first.  0, or the HIP error.
+template <class Kern>
+static inline int raise_lds(Kern k, size_t lds) {
+  if (lds <= 48 * 1024) return 0;
+  return (int)cmf_set_dynamic_lds((const void*)k, (int)lds);
+}
+
+// What every kernel that streams a Jacobian stack asks of it: panels of nc floats per row, sample stride t_b and row stride t_r
+// (floats) that hold a row and keep every row 16-byte aligned.  True when the stack must be refused (CMF_EINVAL).
+static inline bool bad_panel(const float* t, long long t_b, long long t_r, int nc) {
+  return t_b < nc || t_r < nc || (t_b | t_r) % 4 || (uintptr_t)t % 16;
+}
+
 // sum over the 64 lanes of a wavefront (every lane gets the total)
 __device__ __forceinline__ float wave_sum(float v) {
 #pragma unroll

@@ -370,10 +370,7 @@ int launch_step(size_t lds, const float* t, long long t_b, long long t_r, int n_
                 const float* jtj, const float* cross, const float* xhat, const double* damping, double* grad, double* delta,
                 double* stats, double* seg2, int* info, double* ws, long long ws_slice, hipStream_t s) {
   auto k = curve_step_kernel<MODE>;
-  if (lds > 48 * 1024) {
-    hipError_t e = cmf_set_dynamic_lds((const void*)k, (int)lds);
-    if (e != hipSuccess) return (int)e;
-  }
+  if (int e = raise_lds(k, lds)) return e;
   hipLaunchKernelGGL(k, dim3(curves), dim3(NT), lds, s, t, t_b, t_r, n_rows, d, LP, P, jtj, cross, xhat, damping, grad, delta, stats,
                      seg2, info, ws, ws_slice);
   CMF_LAUNCH_CHECK();
@@ -394,7 +391,7 @@ extern "C" int cmf_cross_gram(const float* t, long long t_b, long long t_r, int 
                               float* cross, void* stream) {
   if (!t || n_rows <= 0 || !shape_ok(d, points, curves)) return CMF_EINVAL;
   if (nc % 16 || d > nc || nc > MAXD) return CMF_EINVAL;
-  if (t_b < nc || t_r < nc || (t_b | t_r) % 4 || (uintptr_t)t % 16) return CMF_EINVAL;
+  if (bad_panel(t, t_b, t_r, nc)) return CMF_EINVAL;
   if (points == 3) return 0;                      // no pair of neighbouring interior points
   if (!cross || (uintptr_t)cross % 4) return CMF_EINVAL;
   const long long blocks = (long long)curves * (points - 3);
@@ -428,14 +425,13 @@ extern "C" int cmf_curve_step(const float* t, long long t_b, long long t_r, int 
                           nullptr, stats, seg2, info, nullptr, 0, s);
   if (!jtj || !damping || !grad || !delta || !ws || (!cross && points > 3)) return CMF_EINVAL;
   if (!shape_ok(d, points, curves) || nc % 16 || d > nc) return CMF_EINVAL;
-  if (t_b < nc || t_r < nc || (t_b | t_r) % 4 || (uintptr_t)t % 16) return CMF_EINVAL;
+  if (bad_panel(t, t_b, t_r, nc)) return CMF_EINVAL;
   if ((uintptr_t)jtj % 4 || (uintptr_t)cross % 4 || (uintptr_t)damping % 8 || (uintptr_t)grad % 8 || (uintptr_t)delta % 8 ||
       (uintptr_t)ws % 8)
     return CMF_EINVAL;
   const long long slice = slice_doubles(d, points);
   if (ws_doubles < slice * curves) return CMF_EINVAL;
-  int LP = 4;
-  while (4 * LP < nc && LP < 32) LP <<= 1;
+  const int LP = jt_lanes(nc);
   const bool in_lds = d <= LDS_MAXD;
   const size_t big = in_lds ? (size_t)(2 * d + 1) * window_stride(d) : (size_t)d * (d | 1);
   const size_t lds = sizeof(double) * ((size_t)SMALL + big);

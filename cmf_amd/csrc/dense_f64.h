@@ -1,15 +1,20 @@
-// The float64 linear algebra that the per-sample / per-curve manifold kernels share: gn_step.hip, curve_step.hip,
-// shoot_step.hip, transport_step.hip, star_step.hip and second_form.hip.  Every piece is for one workgroup of F64_NT = 256 threads, all of
-// which call it (the barriers inside are unconditional), and is inlined into its caller.
+// The float64 linear algebra that the per-sample / per-curve manifold kernels share: gn_step.hip, weighted_step.hip,
+// shoot_step.hip, transport_step.hip, second_form.hip, curve_step.hip and star_step.hip.  Every piece is
+// for one workgroup of F64_NT = 256 threads, all of which call it (the barriers inside are unconditional), and is inlined into
+// its caller.  tangent_pca.hip and gram_spectrum.hip take row_stride alone.
 //
 // Contraction: this header carries no fp-contract pragma; the helpers take the state in force where the header is INCLUDED.
 // curve_step.hip, transport_step.hip, star_step.hip and second_form.hip include it after their `#pragma clang fp contract(off)` (one
-// rounded operation per multiply and add); gn_step.hip and shoot_step.hip have no pragma and fuse multiply-adds.  Moving an #include across a pragma,
-// or adding a pragma here, changes output bits.
+// rounded operation per multiply and add); gn_step.hip, weighted_step.hip and shoot_step.hip have no pragma and fuse multiply-adds.
+// Moving an #include across a pragma, or adding a pragma here, changes output bits.
 #pragma once
 #include "common.h"
 
 constexpr int F64_NT = 256;
+
+// Row stride (doubles) of an n-column matrix in LDS: odd, so that the column reads of the elimination (16 rows of one column per
+// wave) spread over the banks instead of landing on one.
+inline __host__ __device__ int row_stride(int n) { return n | 1; }
 
 static __device__ __forceinline__ bool not_finite(float v) { return !(fabsf(v) <= __FLT_MAX__); }
 static __device__ __forceinline__ bool not_finite(double v) { return !(fabs(v) <= __DBL_MAX__); }
@@ -56,6 +61,12 @@ static __device__ __forceinline__ int load_lower(const float* __restrict__ G, in
 // sums them in row-group order).  Columns >= d are padding: lanes that hold none of the first d load nothing, and the padding
 // columns of a live lane are neither tested nor folded.  ORs this thread's "a non-finite entry of J" flag into bad (the caller's
 // own flag, not a returned one: the compiler keeps the four loads of the unrolled loop in flight only this way).
+inline int jt_lanes(int nc) {                     // LP: the power of two >= min(nc, 128) / 4, at least 4
+  int LP = 4;
+  while (4 * LP < nc && LP < 32) LP <<= 1;
+  return LP;
+}
+
 template <class S>
 static __device__ __forceinline__ void jt_stream(const float* __restrict__ tp, long long t_r, int n_rows, int d, int LP, double* part,
                                                  S s, int& bad) {
@@ -119,5 +130,59 @@ static __device__ __forceinline__ void back_substitute(const double* A, int LD, 
     if (tid < i) w[tid] -= A[i * LD + tid] * di;
     if (tid == i) out[i] = di;
     __syncthreads();
+  }
+}
+
+// The damped solve of one sample, from "the float64 lower triangle of G is in A (row stride LD, published), thread k < d holds
+// g_k in gk" to the end of the kernel: A = G + lam diag(G) with g as row d, eliminate, back_substitute into dl (d doubles of LDS),
+// delta, and stats = { cost, g^T delta, delta^T G delta, max |g_k| } with the second form from the float32 lower triangle G in
+// global memory (A no longer holds it), element e to thread e mod F64_NT, tree-folded through part (F64_NT doubles).  A refused
+// pivot gives info 1: delta and the two forms NaN, cost and max |g_k| valid.  delta, stats and info point at this sample's outputs.
+static __device__ __forceinline__ void damped_solve(const float* G, int d, double* A, int LD, double gk, double lam, double cost,
+                                                    double* part, double* dl, double* __restrict__ delta,
+                                                    double* __restrict__ stats, int* __restrict__ info) {
+  const int tid = threadIdx.x;
+  const double nan = __builtin_nan("");
+  if (tid < d) {
+    A[d * LD + tid] = gk;
+    const double gkk = A[tid * LD + tid];
+    A[tid * LD + tid] = gkk + lam * gkk;
+  }
+  __syncthreads();
+  const int fail = eliminate(A, LD, d, d, d, 1);
+  const double gmax = block_fold<true>(tid < d ? fabs(gk) : 0.0, part);
+  if (fail) {                                     // uniform
+    if (tid < d) delta[tid] = nan;
+    if (tid == 0) {
+      stats[0] = cost;
+      stats[1] = nan;
+      stats[2] = nan;
+      stats[3] = gmax;
+      info[0] = 1;
+    }
+    return;
+  }
+  back_substitute(A, LD, d, A + d * LD, dl);
+  double gd = 0.0, q = 0.0;
+  if (tid < d) {
+    const double dk = dl[tid];
+    delta[tid] = dk;
+    gd = gk * dk;
+  }
+  for (int e = tid; e < d * d; e += F64_NT) {
+    const int i = e / d, j = e - i * d;
+    if (j <= i) {
+      const double term = (double)G[e] * dl[i] * dl[j];
+      q += j < i ? 2.0 * term : term;
+    }
+  }
+  gd = block_fold<false>(gd, part);
+  q = block_fold<false>(q, part);
+  if (tid == 0) {
+    stats[0] = cost;
+    stats[1] = gd;
+    stats[2] = q;
+    stats[3] = gmax;
+    info[0] = 0;
   }
 }

@@ -13,7 +13,8 @@
 //      which are folded through LDS in row-group order.  The summation order is a function of (n_rows, nc) alone.  Columns >= d
 //      are padding: lanes that hold none of the first d columns load nothing, and the padding columns a live lane loads are
 //      neither tested for NaN nor folded.
-//   3. The lower triangle of G is loaded into the float64 matrix A in LDS, with g as row d below it, and the diagonal is scaled
+//   3. The lower triangle of G is loaded into the float64 matrix A in LDS; from there on the kernel is damped_solve of
+//      dense_f64.h, which weighted_step.hip ends in too: g goes into row d below the triangle and the diagonal is scaled
 //      by 1 + lambda.  The row stride is d | 1: odd, so that the column reads of the elimination (16 rows of one column per
 //      wave) spread over the banks instead of landing on one.
 //   4. Cholesky without square roots on the lower triangle with g as the extra row d (dense_f64.h, eliminate): the pivots p_k
@@ -33,8 +34,6 @@ static_assert(NT == F64_NT, "dense_f64.h is written for this workgroup size");
 constexpr int MAXD = 128;
 constexpr int PART = 4 * NT;                      // doubles: the J^T r partials [row group][4 LP]; the trees use the first NT
 constexpr int SMALL = PART + MAXD;                // + delta [MAXD]; then A [(d + 1) * row_stride(d)]
-
-inline __host__ __device__ int row_stride(int d) { return d | 1; }
 
 template <bool FULL>
 __global__ __launch_bounds__(NT) void gn_step_kernel(const float* __restrict__ t, long long t_b, long long t_r, int n_rows, int d,
@@ -91,54 +90,11 @@ __global__ __launch_bounds__(NT) void gn_step_kernel(const float* __restrict__ t
   if (tid < d) {
     const int RG = NT / LP;
     for (int q = 0; q < RG; ++q) gk += part[q * (4 * LP) + tid];
-    A[d * LD + tid] = gk;
     grad[(long long)b * d + tid] = gk;
-    const double gkk = A[tid * LD + tid];
-    A[tid * LD + tid] = gkk + damping[b] * gkk;
-  }
-  __syncthreads();
-
-  // 4. pivots and multipliers; row d is g
-  const int fail = eliminate(A, LD, d, d, d, 1);
-  const double gmax = block_fold<true>(tid < d ? fabs(gk) : 0.0, part);
-  if (fail) {                                     // uniform
-    if (tid < d) delta[(long long)b * d + tid] = nan;
-    if (tid == 0) {
-      stats[4LL * b] = r2;
-      stats[4LL * b + 1] = nan;
-      stats[4LL * b + 2] = nan;
-      stats[4LL * b + 3] = gmax;
-      info[b] = 1;
-    }
-    return;
   }
 
-  // 5. back substitution on row d
-  back_substitute(A, LD, d, A + d * LD, dl);
-
-  // 6. the two forms
-  double gd = 0.0, q = 0.0;
-  if (tid < d) {
-    const double dk = dl[tid];
-    delta[(long long)b * d + tid] = dk;
-    gd = gk * dk;
-  }
-  for (int e = tid; e < dd; e += NT) {
-    const int i = e / d, j = e - i * d;
-    if (j <= i) {
-      const double term = (double)G[e] * dl[i] * dl[j];
-      q += j < i ? 2.0 * term : term;
-    }
-  }
-  gd = block_fold<false>(gd, part);
-  q = block_fold<false>(q, part);
-  if (tid == 0) {
-    stats[4LL * b] = r2;
-    stats[4LL * b + 1] = gd;
-    stats[4LL * b + 2] = q;
-    stats[4LL * b + 3] = gmax;
-    info[b] = 0;
-  }
+  // 3b - 6. the damped solve and the two forms (dense_f64.h, damped_solve)
+  damped_solve(G, d, A, LD, gk, damping[b], r2, part, dl, delta + (long long)b * d, stats + 4LL * b, info + b);
 }
 
 }  // namespace
@@ -157,17 +113,12 @@ extern "C" int cmf_gauss_newton_step(const float* t, long long t_b, long long t_
   }
   if (!jtj || !damping || !grad || !delta) return CMF_EINVAL;
   if (d < 1 || d > MAXD || nc % 16 || d > nc) return CMF_EINVAL;
-  if (t_b < nc || t_r < nc || (t_b | t_r) % 4 || (uintptr_t)t % 16) return CMF_EINVAL;
+  if (bad_panel(t, t_b, t_r, nc)) return CMF_EINVAL;
   if ((uintptr_t)jtj % 4 || (uintptr_t)damping % 8 || (uintptr_t)grad % 8 || (uintptr_t)delta % 8) return CMF_EINVAL;
-  int LP = 4;
-  while (4 * LP < nc && LP < 32) LP <<= 1;
   const size_t lds = sizeof(double) * ((size_t)SMALL + (size_t)(d + 1) * row_stride(d));
-  if (lds > 48 * 1024) {
-    hipError_t e = cmf_set_dynamic_lds((const void*)gn_step_kernel<true>, (int)lds);
-    if (e != hipSuccess) return (int)e;
-  }
-  hipLaunchKernelGGL(gn_step_kernel<true>, dim3(B), dim3(NT), lds, s, t, t_b, t_r, n_rows, d, LP, jtj, x, xhat, damping, grad, delta,
-                     stats, info);
+  if (int e = raise_lds(gn_step_kernel<true>, lds)) return e;
+  hipLaunchKernelGGL(gn_step_kernel<true>, dim3(B), dim3(NT), lds, s, t, t_b, t_r, n_rows, d, jt_lanes(nc), jtj, x, xhat, damping, grad,
+                     delta, stats, info);
   CMF_LAUNCH_CHECK();
   return 0;
 }

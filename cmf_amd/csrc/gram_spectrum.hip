@@ -26,7 +26,7 @@
 // lowest row on ties) and the columns are written in rank order -- for 64 < d through the LDS tile A has vacated.
 //
 // A sample's result depends on its d x d input alone: no atomics, nothing shared between workgroups.
-#include "common.h"
+#include "dense_f64.h"                             // row_stride alone: none of its float64 helpers is used here
 
 #pragma clang fp contract(off)
 
@@ -39,7 +39,6 @@ constexpr int MAXPAIR = MAXD / 2;
 // LDS before A, in doubles: c, s, new a_pp, new a_qq per pair; eigenvalues and column signs; then p, q per pair and the ranks (ints)
 constexpr int SMALL = 4 * MAXPAIR + 2 * MAXD + (2 * MAXPAIR + MAXD) / 2;
 
-inline __host__ __device__ int row_stride(int d) { return d | 1; }
 
 // VM: 0 = no eigenvectors, 1 = V in LDS, 2 = V in the output slice
 template <int VM>
@@ -213,10 +212,7 @@ __global__ __launch_bounds__(NT) void gram_spectrum_kernel(const float* __restri
 template <int VM>
 int launch(const float* jtj, int d, int B, double* eig, double* vec, int* sweeps, int* info, hipStream_t s) {
   const size_t lds = sizeof(double) * ((size_t)SMALL + (size_t)d * row_stride(d) * (VM == 1 ? 2 : 1));
-  if (lds > 48 * 1024) {
-    hipError_t e = cmf_set_dynamic_lds((const void*)gram_spectrum_kernel<VM>, (int)lds);
-    if (e != hipSuccess) return (int)e;
-  }
+  if (int e = raise_lds(gram_spectrum_kernel<VM>, lds)) return e;
   hipLaunchKernelGGL(gram_spectrum_kernel<VM>, dim3(B), dim3(NT), lds, s, jtj, d, eig, vec, sweeps, info);
   CMF_LAUNCH_CHECK();
   return 0;

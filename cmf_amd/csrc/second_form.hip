@@ -49,7 +49,6 @@ constexpr int SM_ND = SM_S2 + 64;                 // [16] N's diagonal
 constexpr int SM_GU = SM_ND + 16;                 // [MAXM * MAXD] G u_c
 constexpr int SMALL = SM_GU + MAXM * MAXD;        // then the window, which phase 1's partials [row group][4 LP][q] use first
 
-inline __host__ __device__ int row_stride(int d) { return d | 1; }
 inline __host__ __device__ int window(int d, int q) {
   const int a = (d + q) * row_stride(d), b = 4 * NT * q;
   return a > b ? a : b;
@@ -306,13 +305,9 @@ template <int M>
 int launch(const float* t, long long t_b, long long t_r, int n_rows, int nc, int d, int B, const float* jtj, const float* s,
            long long s_b, long long s_r, const double* frame, const double* step, double* second_gram, double* christoffel,
            double* frame_metric, double* stats, int* info, hipStream_t stream) {
-  int LP = 4;
-  while (4 * LP < nc && LP < 32) LP <<= 1;
+  const int LP = jt_lanes(nc);
   const size_t lds = sizeof(double) * ((size_t)SMALL + (size_t)window(d, M * (M + 1) / 2));
-  if (lds > 48 * 1024) {
-    hipError_t e = cmf_set_dynamic_lds((const void*)second_form_kernel<M>, (int)lds);
-    if (e != hipSuccess) return (int)e;
-  }
+  if (int e = raise_lds(second_form_kernel<M>, lds)) return e;
   hipLaunchKernelGGL(second_form_kernel<M>, dim3(B), dim3(NT), lds, stream, t, t_b, t_r, n_rows, d, LP, jtj, s, s_b, s_r, frame, step,
                      second_gram, christoffel, frame_metric, stats, info);
   CMF_LAUNCH_CHECK();
@@ -327,7 +322,7 @@ extern "C" int cmf_second_form(const float* t, long long t_b, long long t_r, int
                                int* info, void* stream) {
   if (!t || !jtj || !s || !frame || !step || !second_gram || !christoffel || !frame_metric || !stats || !info) return CMF_EINVAL;
   if (n_rows <= 0 || B <= 0 || d < 1 || d > MAXD || m < 1 || m > MAXM || m > d || nc % 16 || d > nc) return CMF_EINVAL;
-  if (t_b < nc || t_r < nc || (t_b | t_r) % 4 || (uintptr_t)t % 16) return CMF_EINVAL;
+  if (bad_panel(t, t_b, t_r, nc)) return CMF_EINVAL;
   if (s_b < 16 || s_r < 16 || (s_b | s_r) % 4 || (uintptr_t)s % 16) return CMF_EINVAL;
   if ((uintptr_t)jtj % 4 || (uintptr_t)frame % 8 || (uintptr_t)step % 8 || (uintptr_t)second_gram % 8 || (uintptr_t)christoffel % 8 ||
       (uintptr_t)frame_metric % 8 || (uintptr_t)stats % 8 || (uintptr_t)info % 4)

@@ -27,8 +27,6 @@ static_assert(NT == F64_NT, "dense_f64.h is written for this workgroup size");
 constexpr int MAXD = 128;
 constexpr int SMALL = NT + MAXD;                  // doubles: the tree's partials [NT], out [MAXD]; then A [(d + 1) * row_stride(d)]
 
-inline __host__ __device__ int row_stride(int d) { return d | 1; }
-
 template <bool APPLY>
 __global__ __launch_bounds__(NT) void metric_solve_kernel(const float* __restrict__ jtj, const double* __restrict__ rhs, int d,
                                                            double* __restrict__ out64, float* __restrict__ out32,
@@ -101,10 +99,7 @@ template <bool APPLY>
 int launch(const float* jtj, const double* rhs, int d, int B, double* out64, float* out32, double* stats, int* info,
            hipStream_t s) {
   const size_t lds = sizeof(double) * ((size_t)SMALL + (size_t)(d + 1) * row_stride(d));
-  if (lds > 48 * 1024) {
-    hipError_t e = cmf_set_dynamic_lds((const void*)metric_solve_kernel<APPLY>, (int)lds);
-    if (e != hipSuccess) return (int)e;
-  }
+  if (int e = raise_lds(metric_solve_kernel<APPLY>, lds)) return e;
   hipLaunchKernelGGL(metric_solve_kernel<APPLY>, dim3(B), dim3(NT), lds, s, jtj, rhs, d, out64, out32, stats, info);
   CMF_LAUNCH_CHECK();
   return 0;

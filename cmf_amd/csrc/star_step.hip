@@ -369,12 +369,6 @@ bool shape_ok(int d, int points, int arms, int stars) {
   return slice_doubles(d, points) <= 0x7fffffffffffLL / ((long long)arms * stars);
 }
 
-template <class Kern>
-int raise_lds(Kern k, size_t lds) {
-  if (lds <= 48 * 1024) return 0;
-  return (int)cmf_set_dynamic_lds((const void*)k, (int)lds);
-}
-
 }  // namespace
 
 extern "C" long long cmf_star_step_ws(int d, int points, int arms, int stars) {
@@ -390,7 +384,7 @@ extern "C" int cmf_star_step(const float* t, long long t_b, long long t_r, int n
       !seg2 || !info || !ws)
     return CMF_EINVAL;
   if (n_rows <= 0 || first < 0 || !shape_ok(d, points, arms, stars) || nc % 16 || d > nc) return CMF_EINVAL;
-  if (t_b < nc || t_r < nc || (t_b | t_r) % 4 || (uintptr_t)t % 16) return CMF_EINVAL;
+  if (bad_panel(t, t_b, t_r, nc)) return CMF_EINVAL;
   if ((uintptr_t)jtj % 4 || (uintptr_t)cross % 4 || (uintptr_t)xhat % 4 || (uintptr_t)info % 4) return CMF_EINVAL;
   if ((uintptr_t)weights % 8 || (uintptr_t)damping % 8 || (uintptr_t)grad % 8 || (uintptr_t)grad_centre % 8 || (uintptr_t)delta % 8 ||
       (uintptr_t)delta_centre % 8 || (uintptr_t)arm_stats % 8 || (uintptr_t)seg2 % 8 || (uintptr_t)ws % 8)
@@ -399,8 +393,7 @@ extern "C" int cmf_star_step(const float* t, long long t_b, long long t_r, int n
   const int n_arms = arms * stars;
   if (ws_doubles < slice * n_arms) return CMF_EINVAL;
   hipStream_t s = (hipStream_t)stream;
-  int LP = 4;
-  while (4 * LP < nc && LP < 32) LP <<= 1;
+  const int LP = jt_lanes(nc);
   const float* t0 = t + first * t_b;
   const bool in_lds = d <= LDS_MAXD;
   const size_t lds_f = sizeof(double) * ((size_t)SMALL + (in_lds ? (size_t)(2 * d + 1) * window_stride(d) : 0));

@@ -22,7 +22,7 @@
 // No fused multiply-adds (fp contract off): every operation is one correctly rounded float64 operation in a fixed order, so the
 // numbers are those of a plain float64 emulation of the same sequence (tests/_tangent_pca_emulation.py).  A group's result depends
 // on its own inputs and on (d, K, r) alone: no atomics, nothing shared between workgroups.
-#include "common.h"
+#include "dense_f64.h"                             // row_stride alone: none of its float64 helpers is used here
 
 #pragma clang fp contract(off)
 
@@ -37,7 +37,6 @@ constexpr int MAXPAIR = MAXK / 2;
 constexpr int SCAL = 2;
 constexpr int SMALL = 4 * MAXPAIR + 4 * MAXK + SCAL + (2 * MAXPAIR + MAXK) / 2;
 
-inline __host__ __device__ int row_stride(int n) { return n | 1; }
 
 __global__ __launch_bounds__(NT) void tangent_pca_kernel(const float* __restrict__ jtj, const double* __restrict__ vin,
                                                          const double* __restrict__ win, int d, int K, int r,
@@ -297,10 +296,7 @@ extern "C" int cmf_tangent_pca(const float* jtj, const double* vectors, const do
   if ((uintptr_t)jtj % 4 || (uintptr_t)rank % 4 || (uintptr_t)sweeps % 4 || (uintptr_t)info % 4) return CMF_EINVAL;
   const size_t g = (size_t)d * row_stride(d), m = 2 * (size_t)arms * row_stride(arms);
   const size_t lds = sizeof(double) * ((size_t)SMALL + (g > m ? g : m));
-  if (lds > 48 * 1024) {
-    hipError_t e = cmf_set_dynamic_lds((const void*)tangent_pca_kernel, (int)lds);
-    if (e != hipSuccess) return (int)e;
-  }
+  if (int e = raise_lds(tangent_pca_kernel, lds)) return e;
   hipLaunchKernelGGL(tangent_pca_kernel, dim3(B), dim3(NT), lds, (hipStream_t)stream, jtj, vectors, weights, d, arms, components,
                      variances, directions, scores, covectors, norm2, total, rank, sweeps, info);
   CMF_LAUNCH_CHECK();

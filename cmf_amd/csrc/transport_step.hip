@@ -233,10 +233,7 @@ extern "C" int cmf_transport_chain(const float* jtj, const float* cross, const d
       (uintptr_t)bwd % 8 || (uintptr_t)norm2 % 8 || (uintptr_t)info % 4)
     return CMF_EINVAL;
   const size_t lds = sizeof(double) * ((size_t)MAXD + (size_t)window(d, m));
-  if (lds > 48 * 1024) {
-    hipError_t e = cmf_set_dynamic_lds((const void*)transport_chain_kernel, (int)lds);
-    if (e != hipSuccess) return (int)e;
-  }
+  if (int e = raise_lds(transport_chain_kernel, lds)) return e;
   hipLaunchKernelGGL(transport_chain_kernel, dim3(curves), dim3(NT), lds, (hipStream_t)stream, jtj, cross, w0, d, m, points, out,
                      fwd, bwd, norm2, info);
   CMF_LAUNCH_CHECK();

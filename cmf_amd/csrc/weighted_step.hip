@@ -22,9 +22,9 @@
 //      live rows alone.
 //   3. The tiles are parked in LDS (over the slab: the float64 matrix below aliases all of it) and written out as gram, element
 //      (i, j) with j > i from its mirror (j, i): symmetric bit for bit.
-//   4. As gn_step.hip from here on: the lower triangle of gram is read back from global memory into the float64 matrix A in LDS
-//      (the step solves the equations of the matrix it returns), g is row d, the diagonal is scaled by 1 + lambda, eliminate,
-//      back_substitute (dense_f64.h), and the two forms from the float32 lower triangle.
+//   4. The lower triangle of gram is read back from global memory into the float64 matrix A in LDS (the step solves the equations
+//      of the matrix it returns); the rest is damped_solve of dense_f64.h, which gn_step.hip ends in too: g is row d, the diagonal
+//      is scaled by 1 + lambda, eliminate, back_substitute, and the two forms from the float32 lower triangle.
 //
 // info: 0 ok; 1 a pivot that is not positive and finite (delta, stats[1], stats[2] = NaN; gram, grad, stats[0], stats[3] valid):
 // fewer live rows than d at lambda = 0, an all-zero weight row; 2 a weight that is negative or not finite, or a non-finite value
@@ -41,7 +41,6 @@ constexpr int CH = 4 * NTH;                       // rows per scan chunk
 constexpr int CAP = CH + KC;                      // live-list capacity: a chunk plus the carry (< KC)
 constexpr int SMALL = NTH + MAXD;                 // doubles: the fold / g partials [NTH], delta [MAXD]; then the aliased region
 
-inline __host__ __device__ int row_stride(int d) { return d | 1; }
 inline __host__ __device__ constexpr int slab_stride(int NC) { return NC % 32 == 0 ? NC + 16 : NC; }
 // byte offsets inside the aliased region while J streams: w r [CAP] doubles, row index [CAP] ints, w [CAP] floats, the slab
 constexpr int OFF_LIST = CAP * 8, OFF_W = OFF_LIST + CAP * 4, OFF_SLAB = OFF_W + CAP * 4;
@@ -289,54 +288,11 @@ __global__ __launch_bounds__(NTH) void weighted_step_kernel(const float* __restr
   __syncthreads();                                  // gram is visible to the workgroup; Gp and part are free
   const double c2 = block_fold<false>(cost, part);
 
-  // 4. the float64 matrix from the float32 values just written
+  // 4. the float64 matrix from the float32 values just written, then the damped solve and the two forms (dense_f64.h)
   const int LD = row_stride(d);
   load_lower<false>(G, d, A, LD);
   __syncthreads();
-  if (tid < d) {
-    A[d * LD + tid] = gk;
-    const double gkk = A[tid * LD + tid];
-    A[tid * LD + tid] = gkk + damping[b] * gkk;
-  }
-  __syncthreads();
-
-  const int fail = eliminate(A, LD, d, d, d, 1);
-  const double gmax = block_fold<true>(tid < d ? fabs(gk) : 0.0, part);
-  if (fail) {                                       // uniform
-    if (tid < d) delta[(long long)b * d + tid] = nan;
-    if (tid == 0) {
-      stats[4LL * b] = c2;
-      stats[4LL * b + 1] = nan;
-      stats[4LL * b + 2] = nan;
-      stats[4LL * b + 3] = gmax;
-      info[b] = 1;
-    }
-    return;
-  }
-  back_substitute(A, LD, d, A + d * LD, dl);
-
-  double gd = 0.0, q = 0.0;
-  if (tid < d) {
-    const double dk = dl[tid];
-    delta[(long long)b * d + tid] = dk;
-    gd = gk * dk;
-  }
-  for (int e = tid; e < dd; e += NTH) {
-    const int i = e / d, j = e - i * d;
-    if (j <= i) {
-      const double term = (double)G[e] * dl[i] * dl[j];
-      q += j < i ? 2.0 * term : term;
-    }
-  }
-  gd = block_fold<false>(gd, part);
-  q = block_fold<false>(q, part);
-  if (tid == 0) {
-    stats[4LL * b] = c2;
-    stats[4LL * b + 1] = gd;
-    stats[4LL * b + 2] = q;
-    stats[4LL * b + 3] = gmax;
-    info[b] = 0;
-  }
+  damped_solve(G, d, A, LD, gk, damping[b], c2, part, dl, delta + (long long)b * d, stats + 4LL * b, info + b);
 }
 
 template <int NT>
@@ -350,10 +306,7 @@ int launch_weighted(const float* t, long long t_b, long long t_r, int n_rows, in
   region = region > mat ? region : mat;
   const size_t lds = sizeof(double) * SMALL + region;
   auto k = weighted_step_kernel<NT>;
-  if (lds > 48 * 1024) {
-    hipError_t e = cmf_set_dynamic_lds((const void*)k, (int)lds);
-    if (e != hipSuccess) return (int)e;
-  }
+  if (int e = raise_lds(k, lds)) return e;
   hipLaunchKernelGGL(k, dim3(B), dim3(NTH), lds, s, t, t_b, t_r, n_rows, d, w, x, xhat, damping, gram, grad, delta, stats, info);
   CMF_LAUNCH_CHECK();
   return 0;
@@ -374,7 +327,7 @@ extern "C" int cmf_weighted_gauss_newton_step(const float* t, long long t_b, lon
   }
   if (!damping || !gram || !grad || !delta) return CMF_EINVAL;
   if (d < 1 || d > MAXD || nc % 16 || d > nc) return CMF_EINVAL;
-  if (t_b < nc || t_r < nc || (t_b | t_r) % 4 || (uintptr_t)t % 16) return CMF_EINVAL;
+  if (bad_panel(t, t_b, t_r, nc)) return CMF_EINVAL;
   if ((uintptr_t)gram % 4 || (uintptr_t)damping % 8 || (uintptr_t)grad % 8 || (uintptr_t)delta % 8) return CMF_EINVAL;
 #define CMF_WEIGHTED_CASE(N) \
   case N: return launch_weighted<N>(t, t_b, t_r, n_rows, d, B, w, x, xhat, damping, gram, grad, delta, stats, info, s);
