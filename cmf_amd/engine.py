@@ -1150,6 +1150,59 @@ def weighted_gauss_newton_step(T, w, x, xhat, damping, d=None):
     _timed("weighted_gauss_newton_step", cost, launch)
     return r
 
+
+def _operator_pair(a, xhat):
+    """The checks ``operator_apply`` and ``operator_image`` share; returns (B, M, D)."""
+    _check_tensor("a", a, torch.float32, "(M, D)", lambda t: t.dim() == 2 and t.shape[0] >= 1 and t.shape[1] >= 1)
+    D = a.shape[1]
+    _check_tensor("xhat", xhat, torch.float32, f"(B, ...) of {D} elements per sample",
+                  lambda t: t.dim() >= 2 and int(np.prod(t.shape[1:])) == D, a.device)
+    return xhat.shape[0], a.shape[0], D
+
+
+def operator_image(a, xhat):
+    """yhat (B, M) float32 = a xhat per sample for the operator ``a`` (M, D) float32 and ``xhat`` (B, ...) float32 of D elements
+    per sample, by the image-only mode of the operator kernel (the same arithmetic, bit for bit, as
+    ``operator_apply(...)[1]``): every sum in float64 in a fixed order, rounded once.  One launch, no synchronisation."""
+    B, M, D = _operator_pair(a, xhat)
+    yhat = torch.empty(B, M, dtype=torch.float32, device=a.device)
+    if B == 0:
+        return yhat
+    launch = lambda: _lib.check(_lib.load().cmf_operator_apply(_p(a), M, D, None, 0, 0, 0, B, _p(xhat), None, 0, 0, _p(yhat),
+                                                               _stream()), "cmf_operator_apply")
+    # a float64 multiply and add per element of a and sample; bytes: xhat in, yhat out, a once (every further read is L2's)
+    _timed("operator_image", lambda: (2.0 * B * M * D, 4.0 * (B * (D + M) + M * D)), launch)
+    return yhat
+
+
+def operator_apply(T, a, xhat):
+    """The linear operator ``a`` (M, D) float32 carried through a decode sweep: from the Jacobian stack ``T`` of D
+    rows and ``xhat`` (B, ...) float32 of D elements per sample, (K, yhat) with K = a J per sample -- a ``Tangent`` of M rows in
+    T's layout with T's nc columns (fp32 MFMA, fp32 accumulation; column c of K depends on column c of T alone) -- and yhat (B, M)
+    float32 = a xhat (float64 sums).  What ``gram_cholesky`` and ``gauss_newton_step`` take in place of (T, xhat) for the recovery
+    min_z ||y - a g(z)||^2.  Deterministic per sample; no synchronisation."""
+    _check_tangent(T)
+    B, M, D = _operator_pair(a, xhat)
+    dev = a.device
+    if T.B != B or T.N != D or T.nc % 16 or not 16 <= T.nc <= 512 or T.data.device != dev:
+        raise ValueError(f"T (B = {T.B}, N = {T.N}, nc = {T.nc}) on {T.data.device} must hold 16 <= nc <= 512 columns, nc % 16 == 0, "
+                         f"for the {B} samples of {D} elements of xhat on {dev}")
+    K = Tangent(B, M, T.nc, T.layout, dev)
+    yhat = torch.empty(B, M, dtype=torch.float32, device=dev)
+    if B == 0:
+        return K, yhat
+    launch = lambda: _lib.check(_lib.load().cmf_operator_apply(_p(a), M, D, _p(T.data), T.t_b, T.t_r, T.nc, B, _p(xhat), _p(K.data),
+                                                               K.t_b, K.t_r, _p(yhat), _stream()), "cmf_operator_apply")
+
+    def cost():
+        # fp32 MFMA: 2 M D per column over the whole row tiles of a (16 rows each), plus the image's 2 M D in float64; bytes: J
+        # once per group of 256 rows of a, K out, xhat in, yhat out, a once (its re-reads by every workgroup are L2's)
+        tiles, passes = -(-M // 16), -(-M // 256)
+        return (B * (2.0 * 16 * tiles * D * T.nc + 2.0 * M * D),
+                4.0 * (B * (passes * D * T.nc + M * T.nc + D + M) + M * D))
+    _timed("operator_apply", cost, launch)
+    return K, yhat
+
 #: widest Jacobian ``cross_gram`` / ``curve_step`` take (csrc/curve_step.hip: the elimination window of a curve lives in LDS up to
 #: d = 64 and in a workspace slice up to d = 128)
 GEODESIC_MAX_WIDTH = 128

@@ -9,6 +9,8 @@ started at the encoder's latent.  A step is one decode sweep (x_hat, J), the Gra
     out = proj.project(x.cuda())
     out["distance2"], out["initial_distance2"]          # squared distances in the head's input space, after and before
     out["tangential2"] / out["distance2"]               # share of the remaining residual that is still tangential
+    proj.complete(x.cuda(), weights)                    # the same with missing or unevenly trusted elements
+    proj.recover(y, A, x_init=x0.cuda())                # the same seen through a linear measurement y = A x
 """
 import torch
 
@@ -118,6 +120,10 @@ class ManifoldProjector:
         mode, y = seen[0][0], seen[0][1]
         assert len(seen) == 1 and mode == "extract-latent"
         return y.contiguous(), z.contiguous()
+
+    def head_input(self, x):
+        """The head's input for ``x``: the ``y`` of ``head_input_and_latent``, the space ``recover``'s operator acts on."""
+        return self.head_input_and_latent(x)[0]
 
     def evaluate(self, y, z, lam):
         """Decode with tangents at ``z``, Gram, step kernel: the ``engine.GaussNewtonResult``."""
@@ -241,4 +247,95 @@ class ManifoldProjector:
         return {"latent": z, "reconstruction_head": x_hat, "reconstruction": to_data_space(self.chain, x_hat), "cost": c,
                 "initial_cost": c_0, "tangential2": r.stats[:, 1].contiguous(), "gradient": r.grad,
                 "distance2": E.residual_sqnorm(y, x_hat)[0], "observed": (w > 0).flatten(1).sum(1).to(torch.int32),
+                "accepted": accepted, "damping": lam, "info": r.info}
+
+    def evaluate_through(self, a, y, z, lam):
+        """Decode with tangents at ``z``, the operator kernel, Gram, step kernel on (K, yhat, y): the ``engine.GaussNewtonResult``."""
+        prog = self.head.program
+        x_hat, T = prog.decode(z, tangents=True)
+        K, y_hat = E.operator_apply(T, a, x_hat.contiguous())
+        jtj = E.gram_cholesky(K, prog.d, 1).jtj
+        return E.gauss_newton_step(K, jtj, y, y_hat, lam)
+
+    @torch.no_grad()
+    def recover(self, measurements, operator, init=None, x_init=None, steps=None):
+        """Linear inverse problem on the manifold: minimise ||y - A g(z)||^2 over z for every sample, where the
+        input is seen only through the linear measurement y = A x.
+          ``operator``: A, (M, D) float32, contiguous, on the GPU, shared by the batch; D is the number of elements of the head's
+          input per sample, and A acts on the flattened HEAD-SPACE tensor in the element order of ``reconstruction_head.flatten(1)``
+          -- the space in which ``distance2`` and ``complete``'s cost are measured (``head_input(x)`` maps an input there; an
+          affine wrapper in front of the head can be folded into A and y by the caller).  ``measurements``: y, (B, M) float32 on
+          the same device.  The starting latent is ``init`` (B, d) float32 as it is, else the encoder's latent of ``x_init`` (a
+          tensor like the density's input: a crude back-projection of y), else zeros, the base density's mode; giving both is a
+          ValueError.
+        The loop is ``project``'s -- the same dampings, clamps and strict ``<`` acceptance, a closing evaluation at lambda = 0 --
+        on the measured cost: a step is the decode sweep, the operator kernel (K = A J and yhat = A g(z), neither leaves the
+        device), and the Gram and step kernels on (K, yhat, y) with M rows in place of D.  Returned keys as ``project``'s, except:
+        ``measurement`` (B, M) float32 = A g(latent); ``cost`` and ``initial_cost`` (B,) float64 = ||y - A g(z)||^2 in place of
+        the distances; ``tangential2`` and ``gradient`` from the measured system.
+        With M < d the problem is underdetermined: the Marquardt term still makes every damped step solvable, so the cost falls,
+        but K^T K is singular and the closing evaluation at lambda = 0 reports ``info`` = 1 with NaN ``tangential2`` -- a result,
+        not an error; ``latent`` is one of the minimisers the damping picked.
+        Sub-batches like ``project``; enqueues kernels only, modifies no input and leaves ``head.last_gram`` alone."""
+        steps = self.steps if steps is None else int(steps)
+        prog = self.head.program
+        D = 1
+        for n in self.head.x_shape:
+            D *= int(n)
+
+        def refuse(name, t, want, fits):                              # dtype, shape, contiguity: said before the device is looked at
+            if not isinstance(t, torch.Tensor) or t.dtype != torch.float32 or not fits(t) or not t.is_contiguous():
+                raise ValueError(f"{name} must be a contiguous float32 {want} tensor, got {getattr(t, 'dtype', type(t).__name__)} "
+                                 f"{tuple(getattr(t, 'shape', ()))}"
+                                 f"{' (not contiguous)' if isinstance(t, torch.Tensor) and not t.is_contiguous() else ''}")
+
+        refuse("operator", operator, f"(M, {D})", lambda t: t.dim() == 2 and t.shape[0] >= 1 and t.shape[1] == D)
+        M, dev = operator.shape[0], operator.device
+        refuse("measurements", measurements, f"(B, {M})", lambda t: t.dim() == 2 and t.shape[1] == M)
+        B = measurements.shape[0]
+        if B == 0 or steps < 0:
+            raise ValueError(f"recover needs at least one sample and steps >= 0, got {B} samples and steps = {steps}")
+        if init is not None and x_init is not None:
+            raise ValueError("give init (a starting latent) or x_init (an input to encode), not both")
+        if init is not None:
+            refuse("init", init, f"({B}, {prog.d})", lambda t: tuple(t.shape) == (B, prog.d))
+        if x_init is not None and (not isinstance(x_init, torch.Tensor) or x_init.dim() < 2 or x_init.shape[0] != B):
+            raise ValueError(f"x_init must hold the {B} samples of measurements, got {tuple(getattr(x_init, 'shape', ()))}")
+        for name, v in (("measurements", measurements), ("init", init), ("x_init", x_init)):
+            if v is not None and v.device != dev:
+                raise ValueError(f"{name} must be on operator's device {dev}, got {v.device} (there is no CPU fallback)")
+        E._check_on_gpu("operator", operator)
+        chunk = prog.tangent_chunk(B)
+        with E.scope(self.head.kernels):
+            parts = [self._recover(measurements[i:i + chunk], operator, None if init is None else init[i:i + chunk],
+                                   None if x_init is None else x_init[i:i + chunk], steps) for i in range(0, B, chunk)]
+        return join_parts(parts)
+
+    def _recover(self, y, a, init, x_init, steps):
+        prog = self.head.program
+        if init is not None:
+            z = init.contiguous().clone()
+        elif x_init is not None:
+            z = self.head_input_and_latent(x_init)[1]
+        else:
+            z = torch.zeros(y.shape[0], prog.d, dtype=torch.float32, device=y.device)
+        y = y.contiguous()
+
+        def at(z):                                                    # the state of ``lm_loop``: (z, g(z), A g(z), ||y - A g(z)||^2)
+            x_hat = prog.decode(z, tangents=False)[0].contiguous()
+            y_hat = E.operator_image(a, x_hat)
+            return z, x_hat, y_hat, E.residual_sqnorm(y, y_hat)[0]
+
+        def trial(state, lam):
+            r = self.evaluate_through(a, y, state[0], lam)
+            solved = r.info == 0
+            return solved, at(state[0] + torch.where(solved[:, None], r.delta, torch.zeros_like(r.delta)).float())
+
+        state = at(z)
+        c_0 = state[3].clone()
+        lam = torch.full((y.shape[0],), self.damping, dtype=torch.float64, device=y.device)
+        (z, x_hat, y_hat, c), lam, accepted = lm_loop(state, 3, lam, steps, self.up, self.down, trial)
+        r = self.evaluate_through(a, y, z, torch.zeros_like(lam))
+        return {"latent": z, "reconstruction_head": x_hat, "reconstruction": to_data_space(self.chain, x_hat), "measurement": y_hat,
+                "cost": c, "initial_cost": c_0, "tangential2": r.stats[:, 1].contiguous(), "gradient": r.grad,
                 "accepted": accepted, "damping": lam, "info": r.info}

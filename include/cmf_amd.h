@@ -481,6 +481,23 @@ int cmf_gauss_newton_step(const float* t, long long t_b, long long t_r, int n_ro
 int cmf_weighted_gauss_newton_step(const float* t, long long t_b, long long t_r, int n_rows, int nc, int d, int B,
                                    const float* w, const float* x, const float* xhat, const double* damping, float* gram,
                                    double* grad, double* delta, double* stats, int* info, void* stream);
+/* A linear measurement operator carried through one decode sweep: for the recovery min_z ||y - a g(z)||^2.
+ *   k(b, m, c) = sum_i a[m][i] t(b, i, c)  for every column c < nc  (the Jacobian stack K_b = a J_b of M rows),
+ *   yhat[b][m] = fl32(sum_i a[m][i] xhat[b][i]).
+ *   a [M][D] float32, row-major, contiguous, shared by the batch; any M, D >= 1 (a row need not be 16-byte aligned).
+ *   t, t_b, t_r, nc: the Jacobian stack of D rows as cmf_gauss_newton_step takes it (both layouts through the two strides);
+ *     k, k_b, k_r: a stack of M rows and the same nc, written whole.  Column c of k depends on column c of t alone: what the
+ *     padding columns of t hold -- NaN included -- stays in the padding columns of k.  Products and sums are fp32
+ *     (v_mfma_f32_16x16x4_f32); the order of accumulation along i is a function of D alone.
+ *   xhat [B][D], yhat [B][M] float32, contiguous.  The sum of yhat runs in float64 in a fixed order and is rounded once.
+ * Image-only mode, t == NULL: only yhat is written -- the same bits as the full mode gives; t_b, t_r, nc, k, k_b, k_r are ignored.
+ * There is no info output: non-finite values propagate by IEEE rules (cmf_gauss_newton_step reports them as info 2).
+ * A sample's outputs are a function of its own inputs, of a and of (M, D, nc) alone: no atomics, independent of B, of its position
+ * in the batch and of the order in which workgroups finish, and they repeat bit for bit.
+ * M, D, B >= 1, a, xhat, yhat not NULL; with t: k not NULL, nc % 16 == 0, 16 <= nc <= 512, the strides of t and of k >= nc and
+ * % 4 == 0, t and k 16-byte aligned.  Anything else: CMF_EINVAL.  No allocation, no synchronisation.                          */
+int cmf_operator_apply(const float* a, int M, int D, const float* t, long long t_b, long long t_r, int nc, int B,
+                       const float* xhat, float* k, long long k_b, long long k_r, float* yhat, void* stream);
 /* One damped Gauss-Newton step on whole discretised curves with fixed end points.  A curve has `points` = P >= 3
  * points, N = P - 1 segments and M = P - 2 interior points; samples are curve-major: point i of curve c is sample c P + i of the
  * Jacobian stack t, of jtj and of xhat.  With r_i = xhat_{i+1} - xhat_i:
