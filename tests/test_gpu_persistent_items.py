@@ -37,6 +37,7 @@ import torch
 import torch.nn.functional as F
 
 import _persistent_items as P
+import _wgrad_elements as WE
 
 pytestmark = pytest.mark.gpu
 
@@ -503,6 +504,15 @@ def _rel(a, b):
     return float((a - b).abs().max() / b.abs().max().clamp_min(1e-30))
 
 
+def _check_wgrad_elements(label, dw, prev, xe, gb, fac, weights, arithmetic, R):
+    """Every entry of the accumulated gradient within  c A + 2^-24 (|prev| + |want|)  of float64 (tests/_wgrad_elements.py): the
+    copies are exact power-of-two multiples of their base samples, so want and A of the batch are those of the base samples with x
+    times the copies' summed scales."""
+    xw = xe.double() * weights.view(-1, 1, 1, 1, 1)
+    want, A = WE.reference(xw, gb, None if fac is None else fac.double(), prev)
+    WE.check_elements(label, dw.t.view(prev.shape).cpu(), want, A, prev, arithmetic, R, tag="PERSISTENT_ITEMS")
+
+
 def _wgrad_reference(xb, gb, fac, weights, cout, cin):
     """float64 autograd of  sum_b weights_b <gy_b, conv(F x_b)>  with respect to w (at w = 0: the product is linear in w)."""
     w = torch.zeros(cout, cin, 3, 3, dtype=torch.float64, requires_grad=True)
@@ -526,7 +536,8 @@ _WGRAD = [
 @pytest.mark.parametrize("precision,cin,cout,H,W,nc,fmode,layout,regime", _WGRAD)
 def test_weight_gradient_many_rows_per_workgroup(precision, cin, cout, H, W, nc, fmode, layout, regime):
     """dW of <gy, conv(F x)> accumulated into a non-zero gradient, against float64 autograd: the split kernel (rows dealt XCD-aware)
-    and the fp32 row-walking kernel (contiguous blocks of rows), every workgroup walking several image rows."""
+    and the fp32 row-walking kernel (contiguous blocks of rows), every workgroup walking several image rows.  Max-norm, and every
+    entry within c A + 2^-24 (|prev| + |want|), A = sum |gy| |F x| (tests/_wgrad_elements.py)."""
     from cmf_amd import engine as E
     split = precision == "bf16x3"
     label = f"wgrad {precision} {H}x{W} ci{cin} co{cout} nc{nc} {fmode} {layout}"
@@ -562,6 +573,7 @@ def test_weight_gradient_many_rows_per_workgroup(precision, cin, cout, H, W, nc,
     err = _rel(got, want)
     print(f"PERSISTENT_ITEMS {label}: max-norm error {err:.2e} (bound {5e-5 if split else 2e-5:.0e})")
     assert err < (5e-5 if split else 2e-5), (label, err)
+    _check_wgrad_elements(label, dw, prev, torch.relu(xb) if fmode == "self" else xb, gb, fac, weights, precision, np_ * H * W * nc)
 
 
 @pytest.mark.parametrize("H,W,fmode,nprob,regime", [(14, 14, "self", 5, "multi"), (16, 16, "none", 3, "multi"), (4, 14, "self", 5, "lt8"),
@@ -581,12 +593,14 @@ def test_batched_weight_gradient_many_rows_per_workgroup(H, W, fmode, nprob, reg
     gs = C * HW * 16
     to_dev = lambda t: t.reshape(t.shape[0], C, HW, 2, 16).permute(0, 3, 1, 2, 4).contiguous().reshape(-1)   # [sample][slice][channel][pixel][16]
     weights = torch.zeros(period, dtype=torch.float64).index_add_(0, base_idx.cpu(), scale.cpu().double())
-    xs, gys, dws, prevs, wants = [], [], [], [], []
+    xs, gys, dws, prevs, wants, xes, gbs = [], [], [], [], [], [], []
     for p in range(nprob):
         gen = torch.Generator().manual_seed(100 * H + p)
         xb = torch.randn(period, C, H, W, nc, generator=gen)
         gb = torch.randn(period, C, H, W, nc, generator=gen)
         wants.append(_wgrad_reference(torch.relu(xb) if fmode == "self" else xb, gb, torch.ones(period, C, H, W), weights, C, C))
+        xes.append(torch.relu(xb) if fmode == "self" else xb)
+        gbs.append(gb)
         xs.append(to_dev(xb.cuda()[base_idx] * scale.view(-1, 1, 1, 1, 1)))
         gys.append(to_dev(gb.cuda()[base_idx]))
         prevs.append(torch.randn(C, C, 3, 3, generator=gen))
@@ -601,4 +615,5 @@ def test_batched_weight_gradient_many_rows_per_workgroup(H, W, fmode, nprob, reg
         err = _rel(dws[p].t.view(C, C, 3, 3).cpu() - prevs[p], wants[p])
         worst = max(worst, err)
         assert err < 5e-5, (label, p, err)
+        _check_wgrad_elements(f"{label} problem {p}", dws[p], prevs[p], xes[p], gbs[p], None, weights, "bf16x3", np_ * H * W * nc)
     print(f"PERSISTENT_ITEMS {label}: max-norm error {worst:.2e} (bound 5e-05)")
