@@ -191,8 +191,9 @@ class AffineCouplingBijection(Bijection):
         if (not zero_in and (T is None or (ncols is not None and ncols <= 15 and lj is None))
                 and E.mlp_coupler_supported(self.net, view, T, 2 * self.cmod)):
             return E.mlp_coupler(self.net, z, T, view, self.maps(z.device), decode=True, lj=lj, ncols=ncols)
-        # the split-precision tangent pass reads relu' from bit masks written by the primal pass (engine.BitMask)
-        c = self._primal(z, view, False if T is None else ("bits" if E.cfg().tangent == "bf16x3" else True), zero_in)
+        # "sweep": what the tangent pass reads best -- the split-precision one takes relu' from bit masks written by the primal pass
+        # (engine.CouplerPlan.acts)
+        c = self._primal(z, view, False if T is None else "sweep", zero_in)
         if T is not None:
             self._tangent(T, c, view, seed_columns)
         E.acl_primal(z, c.y, self.maps(z.device), decode=True, lj=lj)

@@ -187,8 +187,9 @@ def _use_bf16x3(taps, cin, W, transpose, H=None, cout=64):
 
 
 def _shape_ok_bf16x3(taps, cin, W, transpose, H=None, cout=64):
-    """Shapes the split-precision kernel is built for: whole 2 x 14 (or 2 x 8) pixel tiles, whole 64- (or one 32-) channel groups."""
-    return (taps == 9 and cin % 8 == 0 and cin % 32 == 0 and ((W % 14 == 0 and (H is None or H % 2 == 0)) or (W % 8 == 0 and (H is None or H % 4 == 0)))
+    """Shapes the split-precision kernel is built for: whole 2 x 14 (or 2 x 8) pixel tiles, whole 64- (or one 32-) channel groups --
+    the same for a conv and its transpose (``transpose`` is not read: the tests call this with it, by position)."""
+    return (taps == 9 and cin % 32 == 0 and ((W % 14 == 0 and (H is None or H % 2 == 0)) or (W % 8 == 0 and (H is None or H % 4 == 0)))
             and (cout % 64 == 0 or cout == 32))
 
 
@@ -1888,10 +1889,11 @@ def linear_primal(x, weight, bias, relu_in=False, res=None):
 
 class GroupedBatch:
     """(B, F) tensors with 16 samples in the 16 column slots of the tangent-conv kernels -- (G, F, 16), viewed as ONE image row of
-    G pixels -- for the backward of small linear layers (MLP couplers, the nsf prior's MADE and LULinear) on those kernels."""
+    G pixels -- for the backward of small linear layers (MLP couplers, the nsf prior's MADE and LULinear) on those kernels; or (B, C, H,
+    W) tensors as (G, C, HW, 16) images (ResNet couplers).  Zero-padded to a multiple of ``multiple`` samples (CouplerPlan.multiple)."""
 
-    def __init__(self, B, device):
-        self.B, self.Bp, self.dev = B, (B + 15) // 16 * 16, device
+    def __init__(self, B, device, multiple=16):
+        self.B, self.Bp, self.dev = B, (B + multiple - 1) // multiple * multiple, device
         self.G = self.Bp // 16
 
     def pack(self, t):
@@ -1906,6 +1908,10 @@ class GroupedBatch:
     @staticmethod
     def strides(c):
         return (0, 16, c * 16)                               # (np, chan, px)
+
+    @staticmethod
+    def image_strides(c, HW):
+        return (c * HW * 16, HW * 16, 16)                    # (np, chan, px) of a grouped image tensor (G, c, HW, 16)
 
     def linear_backward(self, x_g, dy_g, weight, cin, cout, dw=None, db=None, relu_in=False, fo_g=None, res_g=None):
         """y = W [relu](x) + b on grouped tensors: dw += sum dy (x) [relu](x), db += sum dy, returns W^T dy (optionally
@@ -2031,7 +2037,7 @@ def _resnet_parts(net):
 def net_primal(net, z, view, need_acts=True):
     """Primal forward of a coupler network on the current tensor ``z`` (B, *geom.shape).
     Returns (y (B, cout, ...), g or None, acts: activation tensors the tangent pass differentiates through;
-    ``need_acts=False`` (encode pass, sampling) skips preparing them)."""
+    ``need_acts=False`` (encode pass, sampling) skips preparing them; the other forms of a ResNet coupler: CouplerPlan.acts)."""
     geo, B, dev = view.geom, z.shape[0], z.device
     if net.kind == "resnet":
         conv0, blocks, convf = _resnet_parts(net)
@@ -2040,9 +2046,9 @@ def net_primal(net, z, view, need_acts=True):
         a = new(hid)
         conv_primal(z, view.chan_off * HW, geo.C * HW, view.chan_step * HW, 1, conv0.weight, 9, None, a, hid * HW, HW, 1,
                     B, view.cin, hid, H, W, imode=F_RAW if view.mask is not None else F_NONE, mask=view.mask, f_c=HW, f_px=1)
-        if B % 16 == 0 and _shape_ok_bf16x3(9, hid, W, False, H, hid):
-            return _resnet_primal_grouped(net, blocks, convf, a, B, hid, cout, H, W, need_acts)
-        need_acts = True if need_acts == "train" else need_acts
+        plan = resnet_coupler_plan(net, view, B, None, need_acts)
+        if plan.grouped:
+            return _resnet_primal_grouped(net, blocks, convf, a, B, hid, cout, H, W, plan)
         acts = [a]
         for blk in blocks:
             c1 = new(hid)
@@ -2108,9 +2114,8 @@ class BitMask:
 class ActList(list):
     """Activations of a ResNet coupler kept for TRAINING: the elements are what the tangent pass and the reverse sweep read (the
     float a_0, relu' BitMasks of the hidden activations, the last activation as floats -- the "bits" form), and ``grouped`` holds
-    ALL of them as the sample-grouped float tensors (B/16, C, HW, 16) the primal pass produced, which is what
-    ``net_primal_backward`` reads.  (Before: 17 activations per coupler regrouped to the per-sample layout after the forward pass
-    and back again in the backward pass -- 850 launches per training step.)"""
+    ALL of them as the sample-grouped float tensors (B/16, C, HW, 16) the primal pass produced, which is what ``net_primal_backward``
+    reads (else: 17 activations per coupler regrouped after the forward pass and back in the backward pass, 850 launches per step)."""
     grouped = None
 
 
@@ -2118,44 +2123,31 @@ def train_acts_mode(net, view, B, T=None, nc=None):
     """``need_acts`` for a training forward: "train" (ActList) where every consumer can work from bit masks and grouped floats,
     else True (per-sample float activations).  ``T`` = the tangent stack of the sweep that will read the activations, or ``nc``
     = its column slots when the sweep comes later (primal-only pass)."""
-    nc = T.nc if T is not None else nc
-    if net.kind != "resnet" or B % 32 or cfg().primal == "bf16x3":        # (the bf16 split kernel writes no bit masks)
-        return True
-    conv0 = _resnet_parts(net)[0]
-    hid, H, W = conv0.out_channels, view.geom.H, view.geom.W
-    if hid % 64 or not _shape_ok_bf16x3(9, hid, W, True, H, hid):
-        return True
-    if nc is not None and (cfg().tangent != "bf16x3" or nc % 32):
-        return True
-    return "train"
+    return True if net.kind != "resnet" else resnet_coupler_plan(net, view, B, T.nc if T is not None else nc, "train-if-possible").acts
 
 
-def _resnet_primal_grouped(net, blocks, convf, a0, B, hid, cout, H, W, need_acts):
+def _range_chain(on, nb, first):
+    """The fp16 split kernel's input-range chain over a coupler's 2 ``nb`` hidden convs, forward or backward: word i = max |tensor i| (word
+    0 by a reduction over ``first``, the others raised by the conv that stores the tensor, whose one reader is the next conv); a conv scales
+    its input by the power of two that puts that maximum in [2^13, 2^14).  -> i: conv i's amax_in / amax_out keywords (none if not ``on``)."""
+    if not on:
+        return lambda i: {}
+    rng = torch.zeros(2 * nb + 1, dtype=torch.float32, device=first.device)
+    absmax(first, rng[0:1])
+    return lambda i: dict(amax_in=rng[i:i + 1], amax_out=rng[i + 1:i + 2])
+
+
+def _resnet_primal_grouped(net, blocks, convf, a0, B, hid, cout, H, W, plan):
     """Hidden 3x3 convs of the primal ResNet through the TANGENT conv kernels: the 16 column slots carry 16 samples (relu
-    applied elementwise on load, bias as per-channel constant); ``cfg().primal`` picks the kernel (KernelConfig).
-    need_acts: False (encode pass, sampling), True (float activations in the standard layout: fp32 tangent path, reverse
-    sweep) or "bits" (the split-precision tangent pass follows: the fp32 kernel writes relu' bit masks next to each
-    activation, 1/32 of the bytes, and nothing is regrouped but the last activation, which the 1x1 conv reads as floats)."""
+    applied elementwise on load, bias as per-channel constant); ``plan`` (CouplerPlan) names the kernel, whether it writes relu'
+    bit masks next to each activation, and the form the activations are handed out in."""
     HW, G, dev = H * W, B // 16, a0.device
-    pn = (hid * HW * 16, HW * 16, 16)                       # (np, chan, px) strides of a grouped tensor
+    pn = GroupedBatch.image_strides(hid, HW)
     new = lambda: torch.empty(G * hid * HW * 16, dtype=torch.float32, device=dev)
-    train = need_acts == "train"                          # ActList: the "bits" form + the grouped floats
-    prec = cfg().primal
-    if (prec == "f16x3" and hid % 64) or (prec in ("f16x3", "bf16x3") and hid > 64):
-        # the split kernels work on whole 64-channel groups and fetch the bias of ONE group per launch (cmf_conv_tangent_f16x3
-        # returns CMF_EINVAL for a bias with cout > 64): wider networks (g_hidden_channels 128, 192, ...) take the fp32 kernel
-        prec = "f32"
-    bits = (need_acts == "bits" or train) and prec != "bf16x3" and hid % 16 == 0
+    prec, bits, need_acts = plan.arith, plan.masks, plan.acts
     a = primal_regroup(a0, True)
     acts, masks = [a], []
-    # fp16 split: the input-range chain.  Word i = max |activation i| (word 0 by a reduction over a_0, the others raised by the
-    # conv that stores the activation); a conv scales its input by the power of two that puts that maximum in [2^13, 2^14)
-    # before the fp16 split.  A residual block's output is read by the next block's conv1 only, its conv1 output by conv2 only.
-    rng = None
-    if prec == "f16x3":
-        rng = torch.zeros(2 * len(blocks) + 1, dtype=torch.float32, device=dev)
-        absmax(a, rng[0:1])
-    ax = lambda i: dict(amax_in=rng[i:i + 1], amax_out=rng[i + 1:i + 2]) if rng is not None else {}
+    ax = _range_chain(prec == "f16x3", len(blocks), a)
     for k, blk in enumerate(blocks):
         c1, a2 = new(), new()
         m1, m2 = (BitMask(B, HW, hid, dev), BitMask(B, HW, hid, dev)) if bits else (None, None)
@@ -2164,29 +2156,25 @@ def _resnet_primal_grouped(net, blocks, convf, a0, B, hid, cout, H, W, need_acts
                      precision=prec, **mo(m1), **ax(2 * k))
         conv_tangent(c1, 0, *pn, blk.conv2.weight, 9, a2, *pn, G, hid, hid, H, W, 16, fmode=F_SELF_RELU, bias=blk.conv2.bias,
                      res_t=a, precision=prec, **mo(m2), **ax(2 * k + 1))
-        acts += [c1, a2]
-        masks += [m1, m2]
-        a = a2
+        acts, masks, a = acts + [c1, a2], masks + [m1, m2], a2
     # 1x1 + ScaledTanh on the grouped tensor: a 1x1 conv does not care that "pixels" are (pixel, sample) pairs
     yg = torch.empty(G * cout * HW * 16, dtype=torch.float32, device=dev)
     gg = torch.empty_like(yg)
     conv_primal(a, 0, hid * HW * 16, HW * 16, 1, convf.weight, 1, convf.bias, yg, cout * HW * 16, HW * 16, 1, G, hid, cout,
-                1, HW * 16, imode=F_RELU, omode=O_STANH, sw=net.weights.detach().reshape(-1), sb=net.bias.detach().reshape(-1),
-                g=gg)
+                1, HW * 16, imode=F_RELU, omode=O_STANH, sw=net.weights.detach().reshape(-1), sb=net.bias.detach().reshape(-1), g=gg)
     y = primal_regroup(yg.view(G, -1), False).view(B, cout, H, W)
     g = primal_regroup(gg.view(G, -1), False).view(B, cout, H, W)
     if not need_acts:
         return y, g, None
     std_of = lambda t: primal_regroup(t.view(G, -1), False).view(B, hid, H, W)
-    if train:
-        out = ActList([a0] + masks[:-1] + [std_of(acts[-1])] if bits else [a0] + [std_of(t) for t in acts[1:]])
+    # Bit masks: nothing is regrouped but the last activation, which the 1x1 conv reads as floats.  Floats: the tangent pass reads
+    # relu' per (channel, pixel) of ONE sample, and from the grouped layout every such read is its own 64-byte line (measured:
+    # tangent convs 3.1 -> 4.5 ms); regrouping the 17 saved activations costs ~6 ms / elbo.
+    out = [a0] + masks[:-1] + [std_of(acts[-1])] if bits else [a0] + [std_of(t) for t in acts[1:]]
+    if need_acts == "train":                              # ActList: the same elements + the grouped floats
+        out = ActList(out)
         out.grouped = acts
-        return y, g, out
-    if bits:
-        return y, g, [a0] + masks[:-1] + [std_of(acts[-1])]
-    # The tangent pass reads relu' per (channel, pixel) of ONE sample: from the grouped layout every such read is its
-    # own 64-byte line (measured: tangent convs 3.1 -> 4.5 ms); regrouping the 17 saved activations costs ~6 ms / elbo.
-    return y, g, [a0] + [std_of(t) for t in acts[1:]]
+    return y, g, out
 
 
 def _view_rows(T, view):
@@ -2418,6 +2406,62 @@ def resnet_tangent_plan(net, view, nc, layout, acts, training):
     return TangentPlan(filt, front, tail, bool(CHECKERBOARD_TAIL and live))
 
 
+class CouplerPlan(NamedTuple):
+    """What a training step's other passes do with one ResNet coupler: ``resnet_coupler_plan`` decides, ``net_primal``, ``net_cotangent``
+    and ``net_primal_backward`` execute.  Two things stay with the data and the launch on purpose: what the reverse sweep does with the
+    activations it is actually HANDED (a BitMask as it is, floats through ``relu_bits``, also where a caller forced floats), and the
+    per-launch gate inside ``conv_tangent`` / ``conv_tangent_wgrad``, which has the last word on the kernel."""
+    #: primal pass: the hidden convs run on the tangent kernels, 16 samples in the column slots; else per sample on ``conv_primal``
+    grouped: bool
+    #: their arithmetic: KernelConfig.primal, or "f32" where the split kernels do not take the width -- they work on whole 64-channel
+    #: groups (fp16) and fetch the bias of ONE group per launch (cmf_conv_tangent_f16x3 returns CMF_EINVAL for a bias with cout > 64)
+    arith: str
+    #: they write relu' bit masks next to each activation, 1/32 of the bytes (the bf16 split kernel writes none)
+    masks: bool
+    #: what ``net_primal`` hands out.  False: nothing (encode pass, sampling).  True: floats in the standard layout.  "bits": the float a_0,
+    #: BitMasks of the hidden activations, the last activation as floats (the 1x1 conv reads those).  "train": an ActList, the same elements
+    #: (floats without ``masks``) plus the grouped floats.  Requested as one of these, as "sweep" ("bits" for the split-precision tangent
+    #: sweep, which reads relu' from masks, else True) or as "train-if-possible" ("train" where every consumer works from bit masks and
+    #: grouped floats: groups of 32 samples, a split reverse sweep whose weight gradients take bits; else True)
+    acts: object
+    #: reverse sweep: the hidden transposed convs run on the split-precision kernel when the forward ones do -- no input factor, relu' as
+    #: an output BIT MASK, cotangents slice-major like the forward tangents; else fp32 with float factors
+    split: bool
+    #: its hidden weight gradients take relu' as bit masks (the split kernel: column pairs; the fp32 one reads floats)
+    wgrad_bits: bool
+    #: primal backward: samples the batch is padded to.  32: the split-precision weight-gradient kernel contracts column PAIRS of 16, so
+    #: two sample groups are presented as the two slices of one 32-column "sample" (slice stride = group stride)
+    multiple: int
+    #: its 2 K hidden weight (and bias) gradients go out TOGETHER: one alone would leave most of the chip idle -- at a training shard's 2 -
+    #: 4 sample groups 28 - 56 image rows for 256 persistent workgroups (13.7 ms in 320 launches per C3 step at 64 samples)
+    batched: bool
+    #: its hidden data-gradient convs run the fp16 split kernel's backward form, with an input-range chain of its own
+    bwd16: bool
+
+
+def resnet_coupler_plan(net, view, B, nc=None, need_acts=True):
+    """The CouplerPlan of a ResNet coupler ``net`` read through ``view`` on ``B`` samples; ``nc``: column slots of the sweep that reads
+    the activations (None: a primal-only pass), ``need_acts``: the requested activation form (CouplerPlan.acts).  Host logic on shapes
+    and the calling thread's KernelConfig (read on every call) only: no device, no launch, no allocation."""
+    hid, H, W = _resnet_parts(net)[0].out_channels, view.geom.H, view.geom.W
+    tangent, primal = cfg().tangent, cfg().primal
+    tiles, whole = _shape_ok_bf16x3(9, hid, W, False, H, hid), hid % 64 == 0
+    grouped = B % 16 == 0 and tiles
+    arith = "f32" if (primal == "f16x3" and not whole) or hid > 64 else primal
+    split = tangent == "bf16x3" and tiles and whole
+    wgrad_bits = split and nc is not None and nc % 32 == 0
+    if need_acts == "sweep":
+        need_acts = "bits" if tangent == "bf16x3" else True
+    if need_acts == "train-if-possible":
+        need_acts = "train" if (B % 32 == 0 and tiles and whole and primal != "bf16x3" and (nc is None or wgrad_bits)) else True
+    masks = grouped and need_acts in ("bits", "train") and arith != "bf16x3"
+    if (need_acts == "bits" and not masks) or (need_acts == "train" and not grouped):
+        need_acts = True                                  # floats are all the bf16 split kernel and the per-sample convs leave
+    pair = tangent == "bf16x3" and whole                  # (the weight-gradient kernel: whatever the image's shape)
+    batched = pair and hid == 64 and (B + 31) // 32 * H < 256
+    return CouplerPlan(grouped, arith, masks, need_acts, split, wgrad_bits, 32 if pair else 16, batched, primal == "f16x3" and whole and tiles)
+
+
 def net_tangent(net, T, view, acts, transpose_packs=False, save=None):
     """Push all Jacobian columns of ``T`` through the coupler network; returns the raw tangent of the network's pre-activation output
     (the ScaledTanh derivative ``g`` is applied by acl_tangent).  ``save`` (a list, training): the input tangent of every conv / linear
@@ -2574,10 +2618,8 @@ def net_cotangent(net, YC, view, acts, Ct, saved=None, grads=None, cross=None):
         hd, hsl = (hid * HW * nc, 16, hid * nc), hid * 16  # the forward pass's slice-major hidden layout (net_tangent)
         fa = dict(fo_np=hid * HW, fo_co=HW, fo_px=1, fomode=F_RELU)
         fr = dict(fmode=F_RELU, f_np=hid * HW, f_ci=HW, f_px=1)
-        # The hidden 3x3 transposed convs run on the split-precision kernel when the forward ones do: no input factor, relu' as
-        # an output BIT MASK (derived from the float activations), cotangents slice-major like the forward tangents; the skip
-        # connection is a separate accumulate (the kernel's residual input would be masked with the product).
-        split = cfg().tangent == "bf16x3" and _shape_ok_bf16x3(9, hid, W, True, H, hid) and hid % 64 == 0
+        plan = resnet_coupler_plan(net, view, B, nc)
+        split = plan.split                                 # (the skip connection is then the kernel's residual IN PLACE, below)
         cd, csl = (hd, hsl) if split else (pn(hid), 16)    # layout of the hidden cotangents
         if train:
             t_in, hs, us = saved[0], saved[1::2], saved[2::2]  # h_0 .. h_K, u_0 .. u_{K-1}
@@ -2589,36 +2631,29 @@ def net_cotangent(net, YC, view, acts, Ct, saved=None, grads=None, cross=None):
         ch = new(hid)
         conv_tangent(YC.data, 0, *pn(cout), convf.weight, 1, ch.data, *cd, B, cout, hid, H, W, nc, fo=acts[-1], y_sl=csl, **fa, **f32)
         u, ch2 = new(hid), (None if split else new(hid))      # the in-place skip connection needs no second cotangent buffer
+        # split kernels: relu' of both activations as bit masks (an ActList's, written by the primal pass, or made from the floats),
+        # shared by the weight gradients (input factor) and the transposed convs (output mask); fp32: the float activations
+        bits_of = lambda t: t if isinstance(t, BitMask) else relu_bits(t)
+        tk = lambda act, bits: dict(fo=bits, transpose=True, x_sl=csl, y_sl=csl) if split else dict(fo=act, **fa, **f32)
+        wf = lambda act, bits: dict(f=bits) if plan.wgrad_bits else dict(f=act, **fr)
         for k in reversed(range(len(blocks))):
             blk, a_in, c1 = blocks[k], acts[2 * k], acts[2 * k + 1]
             # h2 = h + conv2(relu'(c1) . u), u = conv1(relu'(a_in) . h):
             #   c_u = relu'(c1) . conv2^T(c_h2);   c_h = c_h2 + relu'(a_in) . conv1^T(c_u)
-            # split kernels: relu' of both activations as bit masks, shared by the weight gradients (input factor) and the
-            # transposed convs (output mask)
-            bits_of = lambda t: t if isinstance(t, BitMask) else relu_bits(t)      # ActList: written by the primal pass
             b_c1, b_in = (bits_of(c1), bits_of(a_in)) if split else (None, None)
             assert split or not isinstance(c1, BitMask), "bit-mask activations need the split-precision reverse sweep"
-            wf = lambda act, bits: dict(f=bits) if split and nc % 32 == 0 else dict(f=act, **fr)   # (the fp32 kernel reads floats)
             if train:
                 conv_tangent_wgrad(us[k].data, 0, *hd, ch.data, 0, *cd, _grad_of(grads, blk.conv2.weight), 9, B, hid, hid, H, W,
                                    nc, x_sl=hsl, y_sl=csl, **wf(c1, b_c1))
-            if split:
-                conv_tangent(ch.data, 0, *cd, blk.conv2.weight, 9, u.data, *cd, B, hid, hid, H, W, nc, fo=b_c1,
-                             transpose=True, x_sl=csl, y_sl=csl)
-            else:
-                conv_tangent(ch.data, 0, *cd, blk.conv2.weight, 9, u.data, *cd, B, hid, hid, H, W, nc, fo=c1, **fa, **f32)
+            conv_tangent(ch.data, 0, *cd, blk.conv2.weight, 9, u.data, *cd, B, hid, hid, H, W, nc, **tk(c1, b_c1))
             if train:
                 conv_tangent_wgrad(hs[k].data, 0, *hd, u.data, 0, *cd, _grad_of(grads, blk.conv1.weight), 9, B, hid, hid, H, W,
                                    nc, x_sl=hsl, y_sl=csl, **wf(a_in, b_in))
-            if split:
-                # the skip connection IN PLACE: c_h += relu'(a_in) . conv1^T(c_u) -- the kernel starts its accumulators from c_h and
-                # the lanes the mask switches off do not store (a separate accumulate pass cost 17 ms of a 235 ms step)
-                conv_tangent(u.data, 0, *cd, blk.conv1.weight, 9, ch.data, *cd, B, hid, hid, H, W, nc, fo=b_in,
-                             transpose=True, x_sl=csl, y_sl=csl, res_t=ch.data)
-            else:
-                conv_tangent(u.data, 0, *cd, blk.conv1.weight, 9, ch2.data, *cd, B, hid, hid, H, W, nc, res_t=ch.data,
-                             fo=a_in, **fa, **f32)
-                ch, ch2 = ch2, ch
+            # split: the skip connection IN PLACE, c_h += relu'(a_in) . conv1^T(c_u) -- the kernel starts its accumulators from c_h and
+            # the lanes the mask switches off do not store (a separate accumulate pass cost 17 ms of a 235 ms step)
+            dst = ch if split else ch2
+            conv_tangent(u.data, 0, *cd, blk.conv1.weight, 9, dst.data, *cd, B, hid, hid, H, W, nc, res_t=ch.data, **tk(a_in, b_in))
+            ch, ch2 = dst, (None if split else ch)
         # h0 = conv0(mask . v_in)  ->  Ct[view] += mask . conv0^T(c_h0)
         off = view.chan_off * HW * nc
         m = view.mask
@@ -2667,71 +2702,45 @@ def net_primal_backward(net, z, view, acts, y, g, dy, dg, grads, dz):
     """Primal backward of a ResNet coupler network (training): given the cotangents ``dy`` of its output
     ``y = sw tanh(u) + sb`` and ``dg`` of the tangent multiplier ``g`` (from ``acl_cross_terms``; may be None), accumulates
     the gradients of every weight, bias and of the ScaledTanh parameters into ``grads`` and the cotangent of the rows of
-    ``z`` the network read into ``dz``.  ``acts`` = the per-sample float activations ``net_primal(need_acts=True)`` returned.
-    Runs on the tangent-conv kernels with 16 samples in the column slots: transposed packs with the per-column output factor
+    ``z`` the network read into ``dz``.  ``acts`` = what ``net_primal`` returned: per-sample floats (need_acts True), or an ActList
+    ("train"), whose grouped floats are read as they are when the batch needs no padding.  Runs on the tangent-conv kernels with 16
+    samples in the column slots (CouplerPlan.multiple, .batched, .bwd16): transposed packs with the per-column output factor
     (``CMF_F_SELF_RELU`` as fomode), ``cmf_conv_tangent_wgrad`` with the input's own relu, ``cmf_channel_sum`` for biases."""
     assert net.kind == "resnet", "MLP couplers: the tanh layers add second-order cross terms that are not built yet"
     geo, B, dev = view.geom, z.shape[0], z.device
     conv0, blocks, convf = _resnet_parts(net)
     hid, cout, H, W, HW = conv0.out_channels, convf.out_channels, geo.H, geo.W, geo.HW
-    # hidden weight gradients on the split-precision kernel: it contracts column PAIRS of 16, so two sample groups are presented as
-    # the two slices of one 32-column "sample" (slice stride = group stride) -- the batch is padded to a multiple of 32 then
-    pair = cfg().tangent == "bf16x3" and hid % 64 == 0
-    Bp = (B + 31) // 32 * 32 if pair else (B + 15) // 16 * 16
-    G = Bp // 16
-
-    def grp(t):                                            # (B, C, H, W) -> flat grouped (G, C, HW, 16), zero-padded samples
-        t = t.reshape(B, -1)
-        if Bp != B:
-            t = torch.cat([t, torch.zeros(Bp - B, t.shape[1], dtype=t.dtype, device=dev)])
-        return primal_regroup(t.contiguous(), True)
-
-    pn = lambda c: (c * HW * 16, HW * 16, 16)
+    plan = resnet_coupler_plan(net, view, B)
+    pair, batch_wgrads, use16 = plan.multiple == 32, plan.batched, plan.bwd16
+    gb = GroupedBatch(B, dev, plan.multiple)
+    G, grp = gb.G, gb.pack                                 # (B, C, H, W) -> flat grouped (G, C, HW, 16), zero-padded samples
+    pn = lambda c: gb.image_strides(c, HW)
     new = lambda c: torch.empty(G * c * HW * 16, dtype=torch.float32, device=dev)
+    gs = hid * HW * 16                                  # group stride = slice stride of a PAIR of groups: its strides and keywords
+    pp, pk = (2 * gs, HW * 16, 16), dict(fmode=F_SELF_RELU, x_sl=gs, y_sl=gs)
+    pending = []                                        # batch_wgrads: the hidden convs' operands, launched TOGETHER once all exist
 
-    # The 2 K hidden weight gradients of the coupler are independent of each other once their operands exist: they are collected and
-    # launched TOGETHER (cmf_conv_tangent_wgrad_bf16x3_batched) when one of them alone would leave most of the chip idle -- at a
-    # training shard's 2 - 4 sample groups a problem is 28 - 56 image rows for 256 persistent workgroups (13.7 ms in 320 launches of
-    # 43 us per C3 step at 64 samples, 12 ms per C5 step at 32)
-    gs = hid * HW * 16                                  # group stride = slice stride
-    batch_wgrads = pair and (G // 2) * H < 256 and hid == 64
-    pending, pending_bias = [], []
+    def flush_grads():
+        parts = [list(zip(*pending[i:i + _lib.WGRAD_MAX_BATCH])) for i in range(0, len(pending), _lib.WGRAD_MAX_BATCH)]
+        for xs, gys, dws, _ in parts:
+            conv_tangent_wgrad_batched(list(xs), list(gys), list(dws), *pp, *pp, G // 2, hid, hid, H, W, 32, **pk)
+        for _, gys, _, dbs in parts:                    # the hidden convs' bias gradients: one launch too
+            channel_sum_batched(list(gys), *pn(hid), G, hid, HW, 16, list(dbs))
 
-    def flush_wgrads():
-        for i in range(0, len(pending), _lib.WGRAD_MAX_BATCH):
-            part = pending[i:i + _lib.WGRAD_MAX_BATCH]
-            conv_tangent_wgrad_batched([p[0] for p in part], [p[1] for p in part], [p[2] for p in part], 2 * gs, HW * 16, 16,
-                                       2 * gs, HW * 16, 16, G // 2, hid, hid, H, W, 32, fmode=F_SELF_RELU, x_sl=gs, y_sl=gs)
-        pending.clear()
-        for i in range(0, len(pending_bias), _lib.WGRAD_MAX_BATCH):       # the hidden convs' bias gradients: one launch too
-            part = pending_bias[i:i + _lib.WGRAD_MAX_BATCH]
-            channel_sum_batched([p[0] for p in part], *pn(hid), G, hid, HW, 16, [p[1] for p in part])
-        pending_bias.clear()
-
-    def hidden_bias_grad(gy_g, bias):
+    def hidden_grads(x_g, gy_g, conv):                  # weight (3x3, hid -> hid, the input's own relu) and bias gradient
+        dw, db = _grad_of(grads, conv.weight), _grad_of(grads, conv.bias)
         if batch_wgrads:
-            pending_bias.append((gy_g, _grad_of(grads, bias)))
+            return pending.append((x_g, gy_g, dw, db))  # the tensors stay alive until the flush
+        if pair:
+            conv_tangent_wgrad(x_g, 0, *pp, gy_g, 0, *pp, dw, 9, G // 2, hid, hid, H, W, 32, **pk)
         else:
-            channel_sum(gy_g, *pn(hid), G, hid, HW, 16, _grad_of(grads, bias))
-
-    def hidden_wgrad(x_g, gy_g, weight):               # 3x3, hid -> hid, the input's own relu
-        if batch_wgrads:
-            pending.append((x_g, gy_g, _grad_of(grads, weight)))       # the tensors stay alive until the flush
-        elif pair:
-            conv_tangent_wgrad(x_g, 0, 2 * gs, HW * 16, 16, gy_g, 0, 2 * gs, HW * 16, 16, _grad_of(grads, weight), 9, G // 2, hid, hid,
-                               H, W, 32, fmode=F_SELF_RELU, x_sl=gs, y_sl=gs)
-        else:
-            conv_tangent_wgrad(x_g, 0, *pn(hid), gy_g, 0, *pn(hid), _grad_of(grads, weight), 9, G, hid, hid, H, W, 16, fmode=F_SELF_RELU)
+            conv_tangent_wgrad(x_g, 0, *pn(hid), gy_g, 0, *pn(hid), dw, 9, G, hid, hid, H, W, 16, fmode=F_SELF_RELU)
+        channel_sum(gy_g, *pn(hid), G, hid, HW, 16, db)
 
     tr = dict(transpose=True, precision="f32")
-    # hidden 3x3 data-gradient convs: the fp16 split kernel's backward form when the primal pass runs on it (KernelConfig.primal), with
-    # its own input-range chain: word 0 = max |da| by a reduction, the others raised by the conv that stores the cotangent
-    use16 = cfg().primal == "f16x3" and hid % 64 == 0 and _shape_ok_bf16x3(9, hid, W, True, H, hid)
-    rng = torch.zeros(2 * len(blocks) + 1, dtype=torch.float32, device=dev) if use16 else None
-    tr16 = lambda i: (dict(transpose=True, precision="f16x3", amax_in=rng[i:i + 1], amax_out=rng[i + 1:i + 2]) if use16 else tr)
     self_fo = lambda t: dict(fo=t, fo_np=hid * HW * 16, fo_co=HW * 16, fo_px=16, fomode=F_SELF_RELU)
     du = stanh_backward(dy, dg, y, g, net.weights, net.bias, _grad_of(grads, net.weights).view(-1), _grad_of(grads, net.bias).view(-1))
-    kept = getattr(acts, "grouped", None) if Bp == B else None   # ActList: the forward pass's grouped tensors, no regrouping
+    kept = getattr(acts, "grouped", None) if gb.Bp == B else None   # ActList: the forward pass's grouped tensors, no regrouping
     gact = lambda i: kept[i] if kept is not None else grp(acts[i])
     du_g, a_g = grp(du), gact(len(acts) - 1)
     # u = convf(relu(a_K)) + bf
@@ -2739,22 +2748,21 @@ def net_primal_backward(net, z, view, acts, y, g, dy, dg, grads, dz):
     channel_sum(du_g, *pn(cout), G, cout, HW, 16, _grad_of(grads, convf.bias))
     da = new(hid)
     conv_tangent(du_g, 0, *pn(cout), convf.weight, 1, da, *pn(hid), G, cout, hid, H, W, 16, **self_fo(a_g), **tr)
-    if use16:
-        absmax(da, rng[0:1])
+    # hidden 3x3 data-gradient convs: the fp16 split kernel's backward form with its own input-range chain, from max |da| on
+    ax = _range_chain(use16, len(blocks), da)
+    tr16 = lambda i: dict(transpose=True, precision="f16x3", **ax(i)) if use16 else tr
     for j, k in enumerate(reversed(range(len(blocks)))):
         blk = blocks[k]
         a_in, c1 = gact(2 * k), gact(2 * k + 1)
         # a' = a + conv2(relu(c1)) + b2,  c1 = conv1(relu(a)) + b1
-        hidden_wgrad(c1, da, blk.conv2.weight)
-        hidden_bias_grad(da, blk.conv2.bias)
+        hidden_grads(c1, da, blk.conv2)
         dc1 = new(hid)
         conv_tangent(da, 0, *pn(hid), blk.conv2.weight, 9, dc1, *pn(hid), G, hid, hid, H, W, 16, **self_fo(c1), **tr16(2 * j))
-        hidden_wgrad(a_in, dc1, blk.conv1.weight)
-        hidden_bias_grad(dc1, blk.conv1.bias)
+        hidden_grads(a_in, dc1, blk.conv1)
         da2 = new(hid)
         conv_tangent(dc1, 0, *pn(hid), blk.conv1.weight, 9, da2, *pn(hid), G, hid, hid, H, W, 16, res_t=da, **self_fo(a_in), **tr16(2 * j + 1))
         da = da2
-    flush_wgrads()
+    flush_grads()
     # a_0 = conv0(mask . z[view])   (no bias)
     cin, m = view.cin, view.mask
     rows = z.reshape(B, geo.C, HW)[:, view.chan_off::view.chan_step][:, :cin]
@@ -2764,7 +2772,7 @@ def net_primal_backward(net, z, view, acts, y, g, dy, dg, grads, dz):
     dx0 = new(cin)
     fo = dict(fo=m, fo_np=0, fo_co=HW, fo_px=1, fomode=F_RAW) if m is not None else {}
     conv_tangent(da, 0, *pn(hid), conv0.weight, 9, dx0, *pn(cin), G, hid, cin, H, W, 16, **fo, **tr)
-    dz.reshape(B, geo.C, HW)[:, view.chan_off::view.chan_step][:, :cin] += primal_regroup(dx0.view(G, -1), False).view(Bp, cin, HW)[:B]
+    dz.reshape(B, geo.C, HW)[:, view.chan_off::view.chan_step][:, :cin] += gb.unpack(dx0, cin * HW).view(B, cin, HW)
 
 
 def mlp_primal_backward(net, z, view, acts, dy, grads, dz, dh_extra=None):
@@ -2777,17 +2785,8 @@ def mlp_primal_backward(net, z, view, acts, dy, grads, dz, dh_extra=None):
     assert net.kind == "mlp" and view.mask is None
     lins = [m for m in net if isinstance(m, nn.Linear)]
     B, dev = z.shape[0], z.device
-    Bp = (B + 15) // 16 * 16
-    G = Bp // 16
-
-    def grp(t):                                            # (B, F) -> flat grouped (G, F, 16), zero-padded samples
-        t = t.reshape(B, -1)
-        if Bp != B:
-            t = torch.cat([t, torch.zeros(Bp - B, t.shape[1], dtype=t.dtype, device=dev)])
-        return primal_regroup(t.contiguous(), True)
-
-    # a grouped tensor (G, c, 16) as ONE image row of G "pixels" (the call shape of the MLP tangent pass): (np, chan, px) strides
-    pn = lambda c: (0, 16, c * 16)
+    gb = GroupedBatch(B, dev)
+    G, grp, pn = gb.G, gb.pack, gb.strides                 # (B, F) -> (G, F, 16) as ONE image row of G "pixels", as the MLP tangent pass
     rows = z.reshape(B, -1)[:, view.chan_off::view.chan_step][:, :view.cin]
     hs = [grp(rows)] + [grp(a) for a in acts]              # input of every linear layer, grouped
     d_g = grp(dy.reshape(B, -1))
@@ -2804,5 +2803,4 @@ def mlp_primal_backward(net, z, view, acts, dy, grads, dz, dh_extra=None):
             _lib.check(lib.cmf_tanh_backward(_p(dh_g), _p(hs[i]), _p(extra), dh_g.numel(), _p(dh_g), _stream()), "cmf_tanh_backward")
             d_g = dh_g
         else:
-            dh = primal_regroup(dh_g.view(G, -1), False).view(Bp, cin)[:B]
-            dz.reshape(B, -1)[:, view.chan_off::view.chan_step][:, :view.cin] += dh
+            dz.reshape(B, -1)[:, view.chan_off::view.chan_step][:, :view.cin] += gb.unpack(dh_g, cin)
