@@ -11,10 +11,11 @@ from .factory import get_density
 from .geodesic import ManifoldGeodesic
 from .metric_spectrum import MetricSpectrum, effective_rank
 from .metric_stats import MetricStatistics
+from .operators import blur, downsample
 from .projection import ManifoldProjector
 from .non_square_helpers import get_non_square_parameters, get_non_square_train_metrics
 from .schemas import DATA_SHAPES, get_config, get_schema
 
 __all__ = ["get_density", "get_config", "get_schema", "DATA_SHAPES", "get_non_square_train_metrics",
            "get_non_square_parameters", "PrecisionGuard", "MetricStatistics", "MetricSpectrum", "effective_rank",
-           "ManifoldProjector", "ManifoldGeodesic", "ManifoldCurvature"]
+           "ManifoldProjector", "ManifoldGeodesic", "ManifoldCurvature", "blur", "downsample"]

@@ -27,6 +27,13 @@
 // multiply-adds in the order of D, four terms per MFMA, whatever the slab depth: a function of D alone.  All M fits one row group
 // up to M = 256 (then J is read once per launch); beyond that every further group reads J again.  No atomics; nothing is shared
 // between workgroups.
+//
+// cmf_operator_apply_wrapped is the same pair of kernels behind the fused pre-head wrapper v = [logit](wa x + wc) of the image
+// configurations: a acts on the DATA-space value u(v) = (p - wc) / wa, p = sigmoid(v) or v.  The image kernel
+// evaluates u in float64 from the fp32 x_hat in front of its product; a small launch writes the derivative s = du/dv (float64,
+// rounded once) to scale [B][D], and the apply kernel multiplies each staged row of J by its scale value on the way into LDS -- one
+// fp32 multiply per element, the MFMA chain and every zero fill as above.  With (wa, wc, logit) = (1, 0, 0) u is x_hat and s is
+// 1.0f exactly, so both outputs are cmf_operator_apply's bits.
 #include "common.h"
 
 namespace {
@@ -40,8 +47,40 @@ constexpr int IMG_ILP = 4;        // rows a wave of the image kernel sums side b
 // reduction slab depth (rows of J): few row tiles leave the MFMAs of a slab short, so the slab is deeper and more of J is in flight
 constexpr int slab_depth(int nrt) { return nrt <= 4 ? 64 : 32; }
 
+// The fused pre-head wrapper v = [logit](wa x + wc), seen from the head's side in float64.  The sigmoid goes through e = exp(-|v|)
+// <= 1: p = 1 / (1 + e) or e / (1 + e), and p (1 - p) = e / (1 + e)^2 -- no 1 - p next to p = 1, so both keep a relative error of
+// a few 2^-53 over the whole range of v.
+struct Wrapper {
+  double wa, wc;
+  int logit;
+};
+
+// the data-space value u = (p - wc) / wa
+__device__ __forceinline__ double wrapper_data(double v, const Wrapper w) {
+  if (w.logit) {
+    const double e = exp(-fabs(v));
+    v = (v >= 0.0 ? 1.0 : e) / (1.0 + e);
+  }
+  return (v - w.wc) / w.wa;
+}
+
+// its derivative s = du / dv = [p (1 - p)] / wa
+__device__ __forceinline__ double wrapper_slope(double v, const Wrapper w) {
+  if (!w.logit) return 1.0 / w.wa;
+  const double e = exp(-fabs(v)), q = 1.0 + e;
+  return e / (q * q) / w.wa;
+}
+
+__global__ __launch_bounds__(NT) void operator_scale_kernel(const float* __restrict__ xhat, long long n, const Wrapper w,
+                                                            float* __restrict__ scale) {
+  const long long i = (long long)blockIdx.x * NT + threadIdx.x;
+  if (i < n) scale[i] = (float)wrapper_slope((double)xhat[i], w);
+}
+
+template <bool WRAPPED>
 __global__ __launch_bounds__(NT) void operator_image_kernel(const float* __restrict__ a, int M, int D,
-                                                            const float* __restrict__ xhat, float* __restrict__ yhat, int groups) {
+                                                            const float* __restrict__ xhat, float* __restrict__ yhat, int groups,
+                                                            const Wrapper w) {
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   const long long b = blockIdx.x / groups;
   const int m0 = (int)(blockIdx.x % groups) * IMG_ROWS;
@@ -53,7 +92,8 @@ __global__ __launch_bounds__(NT) void operator_image_kernel(const float* __restr
 #pragma unroll
     for (int j = 0; j < IMG_ILP; ++j) acc[j] = 0.0;
     for (int i = lane; i < D; i += 64) {
-      const double xv = (double)xb[i];
+      double xv = (double)xb[i];
+      if constexpr (WRAPPED) xv = wrapper_data(xv, w);
 #pragma unroll
       for (int j = 0; j < IMG_ILP; ++j)
         if (m + 4 * j < m1) acc[j] += (double)a[(long long)(m + 4 * j) * D + i] * xv;
@@ -67,10 +107,13 @@ __global__ __launch_bounds__(NT) void operator_image_kernel(const float* __restr
   }
 }
 
-template <int NRT>
-__global__ __launch_bounds__(NT) void operator_apply_kernel(const float* __restrict__ a, int M, int D, const float* __restrict__ t,
-                                                            long long t_b, long long t_r, int nc, float* __restrict__ k,
-                                                            long long k_b, long long k_r, int slabs, int groups) {
+// SCALED: row i of sample b's J is multiplied by scale[b D + i] on its way into LDS.  The scaled kernel of 13 row tiles -- C3's
+// row group (M = 196, 784) -- is asked to stay at two workgroups per CU like the plain one: left alone it takes 270 registers for
+// the plain kernel's 252, one wave per SIMD; asked, it fits 213 without a spill.
+template <int NRT, bool SCALED>
+__global__ __launch_bounds__(NT, (SCALED && NRT == 13) ? 2 : 1) void operator_apply_kernel(
+    const float* __restrict__ a, int M, int D, const float* __restrict__ t, long long t_b, long long t_r, int nc,
+    const float* __restrict__ scale, float* __restrict__ k, long long k_b, long long k_r, int slabs, int groups) {
   constexpr int KD = slab_depth(NRT);
   constexpr int LDA = KD + 4;                       // LDS row stride of the a slab [m][k]: lanes cl * LDA + kq hit 64 distinct banks
   __shared__ __attribute__((aligned(16))) float As[NRT * 16 * LDA];
@@ -83,6 +126,7 @@ __global__ __launch_bounds__(NT) void operator_apply_kernel(const float* __restr
   const long long b = w / groups;
   const int c0 = slab * CS;
   const float* __restrict__ tb = t + b * t_b;
+  const float* __restrict__ sb = SCALED ? scale + b * D : nullptr;
 
   f32x4 acc[NRT];
 #pragma unroll
@@ -92,6 +136,7 @@ __global__ __launch_bounds__(NT) void operator_apply_kernel(const float* __restr
   constexpr int NJ = KD / 16;                       // 16-byte loads of J per thread and slab
   float ra[NA];
   f32x4 rj[NJ];                                     // rows jr, jr + 16, ... of the slab, columns jc .. jc + 3
+  float rs[SCALED ? NJ : 1];                        // and their scale values
   const int jr = tid >> 4, jc = c0 + 4 * (tid & 15);
   auto fetch = [&](int i0) {
 #pragma unroll
@@ -103,6 +148,7 @@ __global__ __launch_bounds__(NT) void operator_apply_kernel(const float* __restr
     for (int q = 0; q < NJ; ++q) {
       const int i = i0 + jr + 16 * q;
       rj[q] = (i < D && jc < nc) ? *(const f32x4*)(tb + (long long)i * t_r + jc) : f32x4{0.f, 0.f, 0.f, 0.f};
+      if constexpr (SCALED) rs[q] = i < D ? sb[i] : 0.f;
     }
   };
   const bool live = c0 + 16 * wave < nc;            // the wave's column tile exists (uniform per wave)
@@ -115,7 +161,10 @@ __global__ __launch_bounds__(NT) void operator_apply_kernel(const float* __restr
       As[(e / KD) * LDA + e % KD] = ra[q];
     }
 #pragma unroll
-    for (int q = 0; q < NJ; ++q) *(f32x4*)(Js + (jr + 16 * q) * LDJ + 4 * (tid & 15)) = rj[q];
+    for (int q = 0; q < NJ; ++q) {
+      if constexpr (SCALED) rj[q] *= rs[q];         // here, not in fetch: the loads stay in flight under the previous slab's MFMAs
+      *(f32x4*)(Js + (jr + 16 * q) * LDJ + 4 * (tid & 15)) = rj[q];
+    }
     __syncthreads();
     if (i0 + KD < D) fetch(i0 + KD);                // in flight under this slab's MFMAs
     if (live) {
@@ -142,45 +191,71 @@ __global__ __launch_bounds__(NT) void operator_apply_kernel(const float* __restr
     }
 }
 
-template <int NRT>
-int launch_apply(const float* a, int M, int D, const float* t, long long t_b, long long t_r, int nc, int B, float* k, long long k_b,
-                 long long k_r, hipStream_t s) {
+template <int NRT, bool SCALED>
+int launch_apply(const float* a, int M, int D, const float* t, long long t_b, long long t_r, int nc, int B, const float* scale,
+                 float* k, long long k_b, long long k_r, hipStream_t s) {
   const int slabs = cmf_ceil_div(nc, CS), groups = cmf_ceil_div(M, NRT * 16);
   const long long grid = (long long)B * slabs * groups;     // < 2^31: checked by the entry point
-  hipLaunchKernelGGL(operator_apply_kernel<NRT>, dim3((unsigned)grid), dim3(NT), 0, s, a, M, D, t, t_b, t_r, nc, k, k_b, k_r, slabs,
-                     groups);
+  hipLaunchKernelGGL((operator_apply_kernel<NRT, SCALED>), dim3((unsigned)grid), dim3(NT), 0, s, a, M, D, t, t_b, t_r, nc, scale, k,
+                     k_b, k_r, slabs, groups);
   CMF_LAUNCH_CHECK();
   return 0;
 }
 
 // the instantiation with nrt row tiles per workgroup, 1 <= nrt <= MAX_RT
-template <int NRT = 1>
-int dispatch_apply(int nrt, const float* a, int M, int D, const float* t, long long t_b, long long t_r, int nc, int B, float* k,
-                   long long k_b, long long k_r, hipStream_t s) {
+template <bool SCALED, int NRT = 1>
+int dispatch_apply(int nrt, const float* a, int M, int D, const float* t, long long t_b, long long t_r, int nc, int B,
+                   const float* scale, float* k, long long k_b, long long k_r, hipStream_t s) {
   if constexpr (NRT < MAX_RT) {
-    if (nrt > NRT) return dispatch_apply<NRT + 1>(nrt, a, M, D, t, t_b, t_r, nc, B, k, k_b, k_r, s);
+    if (nrt > NRT) return dispatch_apply<SCALED, NRT + 1>(nrt, a, M, D, t, t_b, t_r, nc, B, scale, k, k_b, k_r, s);
   }
-  return launch_apply<NRT>(a, M, D, t, t_b, t_r, nc, B, k, k_b, k_r, s);
+  return launch_apply<NRT, SCALED>(a, M, D, t, t_b, t_r, nc, B, scale, k, k_b, k_r, s);
+}
+
+// What both entry points refuse, and the launches behind them.  ``w`` == nullptr: the plain operator (scale is not looked at).
+int operator_apply(const float* a, int M, int D, const float* t, long long t_b, long long t_r, int nc, int B, const float* xhat,
+                   const Wrapper* w, float* scale, float* k, long long k_b, long long k_r, float* yhat, hipStream_t s) {
+  if (!a || !xhat || !yhat || M < 1 || D < 1 || B < 1) return CMF_EINVAL;
+  if ((uintptr_t)a % 4 || (uintptr_t)xhat % 4 || (uintptr_t)yhat % 4) return CMF_EINVAL;
+  if (t) {
+    if (!k || nc < 16 || nc % 16 || nc > 512) return CMF_EINVAL;
+    if (bad_panel(t, t_b, t_r, nc) || bad_panel(k, k_b, k_r, nc)) return CMF_EINVAL;
+    if (w && (!scale || (uintptr_t)scale % 4)) return CMF_EINVAL;
+  }
+  const int groups = cmf_ceil_div(M, IMG_ROWS);
+  // the larger of the two grids: one workgroup per (sample, slab, 16 rows) at the least
+  if ((long long)B * cmf_ceil_div(M, 16) * (t ? cmf_ceil_div(nc, CS) : 1) > 0x7fffffffLL) return CMF_ERANGE;
+  const long long n = (long long)B * D;
+  if (w && t && (n + NT - 1) / NT > 0x7fffffffLL) return CMF_ERANGE;
+  const dim3 image_grid((unsigned)((long long)B * groups));
+  if (w)
+    hipLaunchKernelGGL(operator_image_kernel<true>, image_grid, dim3(NT), 0, s, a, M, D, xhat, yhat, groups, *w);
+  else
+    hipLaunchKernelGGL(operator_image_kernel<false>, image_grid, dim3(NT), 0, s, a, M, D, xhat, yhat, groups, Wrapper{1.0, 0.0, 0});
+  CMF_LAUNCH_CHECK();
+  if (!t) return 0;                                  // image only: the Jacobian arguments are not looked at
+  if (w) {
+    hipLaunchKernelGGL(operator_scale_kernel, dim3((unsigned)((n + NT - 1) / NT)), dim3(NT), 0, s, xhat, n, *w, scale);
+    CMF_LAUNCH_CHECK();
+  }
+  // the row tiles of a, dealt evenly to the fewest row groups that hold them (M = 784: 49 tiles as 4 groups of 13, not 16)
+  const int tiles = cmf_ceil_div(M, 16), row_groups = cmf_ceil_div(tiles, MAX_RT), nrt = cmf_ceil_div(tiles, row_groups);
+  if (w) return dispatch_apply<true>(nrt, a, M, D, t, t_b, t_r, nc, B, scale, k, k_b, k_r, s);
+  return dispatch_apply<false>(nrt, a, M, D, t, t_b, t_r, nc, B, nullptr, k, k_b, k_r, s);
 }
 
 }  // namespace
 
 extern "C" int cmf_operator_apply(const float* a, int M, int D, const float* t, long long t_b, long long t_r, int nc, int B,
                                   const float* xhat, float* k, long long k_b, long long k_r, float* yhat, void* stream) {
-  if (!a || !xhat || !yhat || M < 1 || D < 1 || B < 1) return CMF_EINVAL;
-  if ((uintptr_t)a % 4 || (uintptr_t)xhat % 4 || (uintptr_t)yhat % 4) return CMF_EINVAL;
-  if (t) {
-    if (!k || nc < 16 || nc % 16 || nc > 512) return CMF_EINVAL;
-    if (bad_panel(t, t_b, t_r, nc) || bad_panel(k, k_b, k_r, nc)) return CMF_EINVAL;
-  }
-  hipStream_t s = (hipStream_t)stream;
-  const int groups = cmf_ceil_div(M, IMG_ROWS);
-  // the larger of the two grids: one workgroup per (sample, slab, 16 rows) at the least
-  if ((long long)B * cmf_ceil_div(M, 16) * (t ? cmf_ceil_div(nc, CS) : 1) > 0x7fffffffLL) return CMF_ERANGE;
-  hipLaunchKernelGGL(operator_image_kernel, dim3((unsigned)((long long)B * groups)), dim3(NT), 0, s, a, M, D, xhat, yhat, groups);
-  CMF_LAUNCH_CHECK();
-  if (!t) return 0;                                  // image only: the Jacobian arguments are not looked at
-  // the row tiles of a, dealt evenly to the fewest row groups that hold them (M = 784: 49 tiles as 4 groups of 13, not 16)
-  const int tiles = cmf_ceil_div(M, 16), row_groups = cmf_ceil_div(tiles, MAX_RT);
-  return dispatch_apply(cmf_ceil_div(tiles, row_groups), a, M, D, t, t_b, t_r, nc, B, k, k_b, k_r, s);
+  return operator_apply(a, M, D, t, t_b, t_r, nc, B, xhat, nullptr, nullptr, k, k_b, k_r, yhat, (hipStream_t)stream);
+}
+
+extern "C" int cmf_operator_apply_wrapped(const float* a, int M, int D, const float* t, long long t_b, long long t_r, int nc, int B,
+                                          const float* xhat, float wa, float wc, int logit, float* scale, float* k, long long k_b,
+                                          long long k_r, float* yhat, void* stream) {
+  // wa == 0 or not finite, wc not finite (a finite float less itself is 0; an infinity or a NaN gives NaN), logit no flag
+  if (wa == 0.f || wa - wa != 0.f || wc - wc != 0.f || (logit != 0 && logit != 1)) return CMF_EINVAL;
+  const Wrapper w{(double)wa, (double)wc, logit};
+  return operator_apply(a, M, D, t, t_b, t_r, nc, B, xhat, &w, scale, k, k_b, k_r, yhat, (hipStream_t)stream);
 }

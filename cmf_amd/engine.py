@@ -12,6 +12,7 @@ Layouts
                                    convolution whose "pixels" are the batch samples
 """
 import ctypes as C
+import math
 import threading
 from typing import NamedTuple
 
@@ -1161,19 +1162,83 @@ def _operator_pair(a, xhat):
     return xhat.shape[0], a.shape[0], D
 
 
+def _operator_wrapper(wrapper):
+    """The fused pre-head triple (wa, wc, logit) as ``cmf_operator_apply_wrapped`` takes it: what it would refuse is said here."""
+    try:
+        wa, wc, logit = wrapper
+        wa, wc = float(wa), float(wc)
+    except (TypeError, ValueError):
+        raise ValueError(f"wrapper must be a (wa, wc, logit) triple, got {wrapper!r}") from None
+    if wa == 0.0 or not math.isfinite(wa) or not math.isfinite(wc) or logit not in (0, 1, False, True):
+        raise ValueError(f"wrapper needs a finite wa != 0, a finite wc and logit in (0, 1), got {wrapper!r}")
+    return wa, wc, int(logit)
+
+
+#: what ``operator_image`` and ``operator_apply`` hand the shared code in place of a wrapper
+_PLAIN = object()
+
+
+def _operator_image(name, a, xhat, wrapper):
+    """``operator_image`` (``wrapper`` is _PLAIN) and ``operator_image_wrapped``: the image-only mode of either entry point."""
+    B, M, D = _operator_pair(a, xhat)
+    w = None if wrapper is _PLAIN else _operator_wrapper(wrapper)
+    yhat = torch.empty(B, M, dtype=torch.float32, device=a.device)
+    if B == 0:
+        return yhat
+    if w is None:
+        launch = lambda: _lib.check(_lib.load().cmf_operator_apply(_p(a), M, D, None, 0, 0, 0, B, _p(xhat), None, 0, 0, _p(yhat),
+                                                                   _stream()), "cmf_operator_apply")
+    else:
+        launch = lambda: _lib.check(_lib.load().cmf_operator_apply_wrapped(_p(a), M, D, None, 0, 0, 0, B, _p(xhat), *w, None, None,
+                                                                           0, 0, _p(yhat), _stream()), "cmf_operator_apply_wrapped")
+    # a float64 multiply and add per element of a and sample; bytes: xhat in, yhat out, a once (every further read is L2's)
+    _timed(name, lambda: (2.0 * B * M * D, 4.0 * (B * (D + M) + M * D)), launch)
+    return yhat
+
+
+def _operator_apply(name, T, a, xhat, wrapper, scale):
+    """``operator_apply`` (``wrapper`` is _PLAIN) and ``operator_apply_wrapped``: the full mode of either entry point."""
+    _check_tangent(T)
+    B, M, D = _operator_pair(a, xhat)
+    w = None if wrapper is _PLAIN else _operator_wrapper(wrapper)
+    dev = a.device
+    if T.B != B or T.N != D or T.nc % 16 or not 16 <= T.nc <= 512 or T.data.device != dev:
+        raise ValueError(f"T (B = {T.B}, N = {T.N}, nc = {T.nc}) on {T.data.device} must hold 16 <= nc <= 512 columns, nc % 16 == 0, "
+                         f"for the {B} samples of {D} elements of xhat on {dev}")
+    if w is not None:
+        if scale is None:
+            scale = torch.empty(B, D, dtype=torch.float32, device=dev)
+        else:
+            _check_tensor("scale", scale, torch.float32, f"({B}, {D})", lambda t: tuple(t.shape) == (B, D), dev)
+    K = Tangent(B, M, T.nc, T.layout, dev)
+    yhat = torch.empty(B, M, dtype=torch.float32, device=dev)
+    if B == 0:
+        return K, yhat, scale
+    if w is None:
+        launch = lambda: _lib.check(_lib.load().cmf_operator_apply(_p(a), M, D, _p(T.data), T.t_b, T.t_r, T.nc, B, _p(xhat),
+                                                                   _p(K.data), K.t_b, K.t_r, _p(yhat), _stream()), "cmf_operator_apply")
+    else:
+        launch = lambda: _lib.check(_lib.load().cmf_operator_apply_wrapped(
+            _p(a), M, D, _p(T.data), T.t_b, T.t_r, T.nc, B, _p(xhat), *w, _p(scale), _p(K.data), K.t_b, K.t_r, _p(yhat), _stream()),
+            "cmf_operator_apply_wrapped")
+
+    def cost():
+        # fp32 MFMA: 2 M D per column over the whole row tiles of a (16 rows each), plus the image's 2 M D in float64; bytes: J
+        # once per group of 256 rows of a, K out, xhat in, yhat out, a once (its re-reads by every workgroup are L2's).  Wrapped:
+        # one more multiply per element of J and pass; xhat once more for scale, scale out and in once per pass
+        tiles, passes = -(-M // 16), -(-M // 256)
+        more = (0.0, 0.0) if w is None else (1.0 * B * passes * D * T.nc, 4.0 * B * D * (2 + passes))
+        return (B * (2.0 * 16 * tiles * D * T.nc + 2.0 * M * D) + more[0],
+                4.0 * (B * (passes * D * T.nc + M * T.nc + D + M) + M * D) + more[1])
+    _timed(name, cost, launch)
+    return K, yhat, scale
+
+
 def operator_image(a, xhat):
     """yhat (B, M) float32 = a xhat per sample for the operator ``a`` (M, D) float32 and ``xhat`` (B, ...) float32 of D elements
     per sample, by the image-only mode of the operator kernel (the same arithmetic, bit for bit, as
     ``operator_apply(...)[1]``): every sum in float64 in a fixed order, rounded once.  One launch, no synchronisation."""
-    B, M, D = _operator_pair(a, xhat)
-    yhat = torch.empty(B, M, dtype=torch.float32, device=a.device)
-    if B == 0:
-        return yhat
-    launch = lambda: _lib.check(_lib.load().cmf_operator_apply(_p(a), M, D, None, 0, 0, 0, B, _p(xhat), None, 0, 0, _p(yhat),
-                                                               _stream()), "cmf_operator_apply")
-    # a float64 multiply and add per element of a and sample; bytes: xhat in, yhat out, a once (every further read is L2's)
-    _timed("operator_image", lambda: (2.0 * B * M * D, 4.0 * (B * (D + M) + M * D)), launch)
-    return yhat
+    return _operator_image("operator_image", a, xhat, _PLAIN)
 
 
 def operator_apply(T, a, xhat):
@@ -1182,27 +1247,24 @@ def operator_apply(T, a, xhat):
     T's layout with T's nc columns (fp32 MFMA, fp32 accumulation; column c of K depends on column c of T alone) -- and yhat (B, M)
     float32 = a xhat (float64 sums).  What ``gram_cholesky`` and ``gauss_newton_step`` take in place of (T, xhat) for the recovery
     min_z ||y - a g(z)||^2.  Deterministic per sample; no synchronisation."""
-    _check_tangent(T)
-    B, M, D = _operator_pair(a, xhat)
-    dev = a.device
-    if T.B != B or T.N != D or T.nc % 16 or not 16 <= T.nc <= 512 or T.data.device != dev:
-        raise ValueError(f"T (B = {T.B}, N = {T.N}, nc = {T.nc}) on {T.data.device} must hold 16 <= nc <= 512 columns, nc % 16 == 0, "
-                         f"for the {B} samples of {D} elements of xhat on {dev}")
-    K = Tangent(B, M, T.nc, T.layout, dev)
-    yhat = torch.empty(B, M, dtype=torch.float32, device=dev)
-    if B == 0:
-        return K, yhat
-    launch = lambda: _lib.check(_lib.load().cmf_operator_apply(_p(a), M, D, _p(T.data), T.t_b, T.t_r, T.nc, B, _p(xhat), _p(K.data),
-                                                               K.t_b, K.t_r, _p(yhat), _stream()), "cmf_operator_apply")
+    return _operator_apply("operator_apply", T, a, xhat, _PLAIN, None)[:2]
 
-    def cost():
-        # fp32 MFMA: 2 M D per column over the whole row tiles of a (16 rows each), plus the image's 2 M D in float64; bytes: J
-        # once per group of 256 rows of a, K out, xhat in, yhat out, a once (its re-reads by every workgroup are L2's)
-        tiles, passes = -(-M // 16), -(-M // 256)
-        return (B * (2.0 * 16 * tiles * D * T.nc + 2.0 * M * D),
-                4.0 * (B * (passes * D * T.nc + M * T.nc + D + M) + M * D))
-    _timed("operator_apply", cost, launch)
-    return K, yhat
+
+def operator_image_wrapped(a, xhat, wrapper):
+    """``operator_image`` in data space: yhat (B, M) float32 = a u(xhat) with u the inverse of the fused pre-head
+    wrapper v = [logit](wa x + wc), ``wrapper`` = (wa, wc, logit), evaluated in float64 in front of the float64 sum.  The same
+    bits as ``operator_apply_wrapped(...)[1]``; with (1, 0, False), ``operator_image``'s.  One launch, no synchronisation."""
+    return _operator_image("operator_image_wrapped", a, xhat, wrapper)
+
+
+def operator_apply_wrapped(T, a, xhat, wrapper, scale=None):
+    """``operator_apply`` in data space, for an operator that acts on the density's input behind the fused pre-head
+    wrapper v = [logit](wa x + wc), ``wrapper`` = (wa, wc, logit): (K, yhat, scale) with scale (B, D) float32 = du/dv at xhat
+    (float64, rounded once), K = a diag(scale) J per sample -- every element of J times its row's scale value in fp32, then
+    ``operator_apply``'s MFMAs -- and yhat = a u(xhat).  ``scale``: an optional (B, D) float32 buffer to write into, for a loop
+    that calls this every step; allocated otherwise.  With (1, 0, False), scale is 1 and (K, yhat) are ``operator_apply``'s bits.
+    Deterministic per sample; no synchronisation."""
+    return _operator_apply("operator_apply_wrapped", T, a, xhat, wrapper, scale)
 
 #: widest Jacobian ``cross_gram`` / ``curve_step`` take (csrc/curve_step.hip: the elimination window of a curve lives in LDS up to
 #: d = 64 and in a workspace slice up to d = 128)

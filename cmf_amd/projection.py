@@ -11,6 +11,7 @@ started at the encoder's latent.  A step is one decode sweep (x_hat, J), the Gra
     out["tangential2"] / out["distance2"]               # share of the remaining residual that is still tangential
     proj.complete(x.cuda(), weights)                    # the same with missing or unevenly trusted elements
     proj.recover(y, A, x_init=x0.cuda())                # the same seen through a linear measurement y = A x
+    proj.recover(y, A, x_init=x0.cuda(), space="data")  # A acts on the density's input, e.g. pixel values
 """
 import torch
 
@@ -19,7 +20,7 @@ from .bijections import AffineBijection, Squeeze2dBijection, ViewBijection, _Ele
 from .densities import BijectionDensity, DataParallelDensity, WrapperDensity
 from .metric_stats import metric_head
 
-__all__ = ["ManifoldProjector"]
+__all__ = ["ManifoldProjector", "data_space_wrapper"]
 
 #: the clamps of the per-sample damping
 DAMPING_MIN, DAMPING_MAX = 1e-12, 1e8
@@ -65,6 +66,34 @@ def to_head_space_weights(chain, w):
             raise NotImplementedError(f"weights cannot be carried through a {type(bijection).__name__} in front of the head: it "
                                       "mixes elements (only elementwise and reshaping bijections are built)")
     return w
+
+
+def data_space_wrapper(chain):
+    """The bijections ``chain`` (``wrapper_bijections``) as (wa, wc, logit, perm): the head's input is [logit](wa x + wc) of the
+    data elements x, taken in the order ``perm`` -- head element r is data element perm[r]; ``perm`` is an int64 tensor on the
+    host, or None for the flat order as it is.  Elementwise bijections fuse as the density's own fused pre-head fuses them
+    (``BijectionDensity._fused_prehead``); a ``ViewBijection`` keeps the flat order and a ``Squeeze2dBijection`` contributes the
+    index map its ``x_to_z`` applies to data (an index map commutes with what acts on every element alike, so it may stand
+    anywhere in the chain).  An elementwise bijection after a logit, an ``AffineBijection`` (one scale per element: DESIGN 9) or
+    any other type: NotImplementedError.  An empty chain gives (1.0, 0.0, False, None)."""
+    wa, wc, logit, perm = 1.0, 0.0, False, None
+    for bijection in chain:
+        if isinstance(bijection, _Elementwise):
+            if logit:
+                raise NotImplementedError(f"a {type(bijection).__name__} after a logit in front of the head is not one fused "
+                                          "pre-head wrapper: recover(space='data') is not built for it")
+            wa, wc, logit = wa * bijection.a, wc * bijection.a + bijection.c, bool(bijection.logit)
+        elif isinstance(bijection, ViewBijection):
+            continue
+        elif isinstance(bijection, Squeeze2dBijection):
+            x2z = torch.from_numpy(bijection._maps._host["x2z"]).long()    # z[r] = x[x2z[r]]
+            perm = x2z if perm is None else perm[x2z]
+        else:
+            raise NotImplementedError(f"recover(space='data') is not built for a {type(bijection).__name__} in front of the head "
+                                      "(only scalar elementwise and reshaping bijections are)")
+    if perm is not None and torch.equal(perm, torch.arange(perm.numel())):
+        perm = None
+    return wa, wc, logit, perm
 
 
 def join_parts(parts):
@@ -249,16 +278,17 @@ class ManifoldProjector:
                 "distance2": E.residual_sqnorm(y, x_hat)[0], "observed": (w > 0).flatten(1).sum(1).to(torch.int32),
                 "accepted": accepted, "damping": lam, "info": r.info}
 
-    def evaluate_through(self, a, y, z, lam):
-        """Decode with tangents at ``z``, the operator kernel, Gram, step kernel on (K, yhat, y): the ``engine.GaussNewtonResult``."""
+    def evaluate_through(self, a, y, z, lam, apply=E.operator_apply):
+        """Decode with tangents at ``z``, the operator kernel ``apply(T, a, x_hat)`` -> (K, yhat), Gram, step kernel on (K, yhat,
+        y): the ``engine.GaussNewtonResult``."""
         prog = self.head.program
         x_hat, T = prog.decode(z, tangents=True)
-        K, y_hat = E.operator_apply(T, a, x_hat.contiguous())
+        K, y_hat = apply(T, a, x_hat.contiguous())
         jtj = E.gram_cholesky(K, prog.d, 1).jtj
         return E.gauss_newton_step(K, jtj, y, y_hat, lam)
 
     @torch.no_grad()
-    def recover(self, measurements, operator, init=None, x_init=None, steps=None):
+    def recover(self, measurements, operator, init=None, x_init=None, steps=None, space="head"):
         """Linear inverse problem on the manifold: minimise ||y - A g(z)||^2 over z for every sample, where the
         input is seen only through the linear measurement y = A x.
           ``operator``: A, (M, D) float32, contiguous, on the GPU, shared by the batch; D is the number of elements of the head's
@@ -276,9 +306,20 @@ class ManifoldProjector:
         With M < d the problem is underdetermined: the Marquardt term still makes every damped step solvable, so the cost falls,
         but K^T K is singular and the closing evaluation at lambda = 0 reports ``info`` = 1 with NaN ``tangential2`` -- a result,
         not an error; ``latent`` is one of the minimisers the damping picked.
+          ``space`` = "data" (DESIGN 4.3p): A acts on the density's INPUT instead -- pixel values, flattened as ``x.flatten(1)``,
+        ``measurements`` = A x --, which is what a blur or a down-sampling is linear in (``cmf_amd.operators`` builds both).
+        The wrapper chain in front of the head must reduce to one fused pre-head v = [logit](wa x + wc) and an index map
+        (``data_space_wrapper``; NotImplementedError otherwise).  The loop and the keys are the same; the operator kernel takes
+        the wrapper along: yhat = A u(g(z)) with u the wrapper's inverse in float64, K = A diag(du/dv) J.  ``measurement`` = A
+        u(g(latent)) with u in float64 (not A applied to the float32 ``reconstruction`` tensor), and ``cost`` and
+        ``initial_cost`` are measured in data-space measurements.  Where the map reorders elements the columns of A are permuted
+        once per call, on the device, into a copy.  With no wrapper (the tabular configurations) both spaces give the same bits.
         Sub-batches like ``project``; enqueues kernels only, modifies no input and leaves ``head.last_gram`` alone."""
         steps = self.steps if steps is None else int(steps)
         prog = self.head.program
+        if space not in ("head", "data"):
+            raise ValueError(f"space must be 'head' or 'data', got {space!r}")
+        wrapper = data_space_wrapper(self.chain) if space == "data" else None
         D = 1
         for n in self.head.x_shape:
             D *= int(n)
@@ -305,13 +346,30 @@ class ManifoldProjector:
             if v is not None and v.device != dev:
                 raise ValueError(f"{name} must be on operator's device {dev}, got {v.device} (there is no CPU fallback)")
         E._check_on_gpu("operator", operator)
+        if wrapper is not None and wrapper[3] is not None:
+            operator = operator.index_select(1, wrapper[3].to(dev))       # acts on head-ordered elements; a copy
         chunk = prog.tangent_chunk(B)
         with E.scope(self.head.kernels):
             parts = [self._recover(measurements[i:i + chunk], operator, None if init is None else init[i:i + chunk],
-                                   None if x_init is None else x_init[i:i + chunk], steps) for i in range(0, B, chunk)]
+                                   None if x_init is None else x_init[i:i + chunk], steps, *self._operator_calls(wrapper))
+                     for i in range(0, B, chunk)]
         return join_parts(parts)
 
-    def _recover(self, y, a, init, x_init, steps):
+    @staticmethod
+    def _operator_calls(wrapper):
+        """(image(a, x_hat) -> yhat, apply(T, a, x_hat) -> (K, yhat)) of one sub-batch: the head-space operator kernel, or
+        (``wrapper`` from ``data_space_wrapper``) the data-space one with one ``scale`` buffer that every step writes anew."""
+        if wrapper is None:
+            return E.operator_image, E.operator_apply
+        triple, held = wrapper[:3], []
+
+        def apply(T, a, x_hat):
+            K, y_hat, scale = E.operator_apply_wrapped(T, a, x_hat, triple, held[0] if held else None)
+            held[:] = [scale]
+            return K, y_hat
+        return (lambda a, x_hat: E.operator_image_wrapped(a, x_hat, triple)), apply
+
+    def _recover(self, y, a, init, x_init, steps, image, apply):
         prog = self.head.program
         if init is not None:
             z = init.contiguous().clone()
@@ -323,11 +381,11 @@ class ManifoldProjector:
 
         def at(z):                                                    # the state of ``lm_loop``: (z, g(z), A g(z), ||y - A g(z)||^2)
             x_hat = prog.decode(z, tangents=False)[0].contiguous()
-            y_hat = E.operator_image(a, x_hat)
+            y_hat = image(a, x_hat)
             return z, x_hat, y_hat, E.residual_sqnorm(y, y_hat)[0]
 
         def trial(state, lam):
-            r = self.evaluate_through(a, y, state[0], lam)
+            r = self.evaluate_through(a, y, state[0], lam, apply)
             solved = r.info == 0
             return solved, at(state[0] + torch.where(solved[:, None], r.delta, torch.zeros_like(r.delta)).float())
 
@@ -335,7 +393,7 @@ class ManifoldProjector:
         c_0 = state[3].clone()
         lam = torch.full((y.shape[0],), self.damping, dtype=torch.float64, device=y.device)
         (z, x_hat, y_hat, c), lam, accepted = lm_loop(state, 3, lam, steps, self.up, self.down, trial)
-        r = self.evaluate_through(a, y, z, torch.zeros_like(lam))
+        r = self.evaluate_through(a, y, z, torch.zeros_like(lam), apply)
         return {"latent": z, "reconstruction_head": x_hat, "reconstruction": to_data_space(self.chain, x_hat), "measurement": y_hat,
                 "cost": c, "initial_cost": c_0, "tangential2": r.stats[:, 1].contiguous(), "gradient": r.grad,
                 "accepted": accepted, "damping": lam, "info": r.info}

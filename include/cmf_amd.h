@@ -498,6 +498,23 @@ int cmf_weighted_gauss_newton_step(const float* t, long long t_b, long long t_r,
  * % 4 == 0, t and k 16-byte aligned.  Anything else: CMF_EINVAL.  No allocation, no synchronisation.                          */
 int cmf_operator_apply(const float* a, int M, int D, const float* t, long long t_b, long long t_r, int nc, int B,
                        const float* xhat, float* k, long long k_b, long long k_r, float* yhat, void* stream);
+/* The same operator in DATA space, behind the fused pre-head wrapper v = [logit](wa x + wc) that cmf_prehead applies in front of the
+ * head: for the recovery min_z ||y - a u(g(z))||^2 with a blur or a down-sampling a, linear in pixel values.  For a
+ * head-space value v:  p = logit ? 1 / (1 + exp(-v)) : v,  u = (p - wc) / wa,  s = du/dv = (logit ? p (1 - p) : 1) / wa.
+ *   yhat[b][m]  = fl32(sum_i a[m][i] u(xhat[b][i])): u in float64 from the fp32 xhat, the sum in float64 in cmf_operator_apply's
+ *     order, rounded once.
+ *   scale[b][i] = fl32(s(xhat[b][i])), s in float64; [B][D] float32, contiguous, caller-owned, written whole.
+ *   k(b, m, c)  = sum_i a[m][i] fl32(scale[b][i] t(b, i, c)): the measured Jacobian a diag(s_b) J_b.  One fp32 multiply per element
+ *     of t on its way to the MFMAs of cmf_operator_apply, which are otherwise unchanged -- the order of accumulation, the columns
+ *     kept apart, what the padding columns hold (NaN times a finite s is NaN).
+ * With (wa, wc, logit) = (1, 0, 0): u is xhat and s is 1.0f exactly, and k and yhat are cmf_operator_apply's, bit for bit.
+ * Image-only mode, t == NULL: only yhat is written -- the same bits as the full mode gives; scale, k and the stack arguments are
+ * ignored.  A sample's outputs are a function of its own inputs, of a, of the triple and of (M, D, nc) alone; no atomics.
+ * Refused with CMF_EINVAL before any launch: what cmf_operator_apply refuses; wa zero or not finite; wc not finite; logit not 0 or
+ * 1; with t, scale NULL or not 4-byte aligned.  No allocation, no synchronisation.                                               */
+int cmf_operator_apply_wrapped(const float* a, int M, int D, const float* t, long long t_b, long long t_r, int nc, int B,
+                               const float* xhat, float wa, float wc, int logit, float* scale, float* k, long long k_b,
+                               long long k_r, float* yhat, void* stream);
 /* One damped Gauss-Newton step on whole discretised curves with fixed end points.  A curve has `points` = P >= 3
  * points, N = P - 1 segments and M = P - 2 interior points; samples are curve-major: point i of curve c is sample c P + i of the
  * Jacobian stack t, of jtj and of xhat.  With r_i = xhat_{i+1} - xhat_i:
