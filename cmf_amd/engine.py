@@ -1153,6 +1153,54 @@ def weighted_gauss_newton_step(T, w, x, xhat, damping, d=None):
     return r
 
 
+class LeverageResult:
+    """Outputs of ``tangent_leverage`` (all on the device): ``cov`` (B, d, d) float64 = gram^-1, symmetric bit for bit, ``lev``
+    (B, N) float64 = j_i^T gram^-1 j_i >= +0.0 per row of J, ``stats`` (B, 2) float64 = [sum_i lev_i, max_i lev_i] (both None
+    with ``rows=False``), ``info`` (B,) int32 (0 ok, 1 non-positive pivot, 2 non-finite input: every output NaN in both cases)."""
+    __slots__ = ("cov", "lev", "stats", "info")
+
+
+def tangent_leverage(T, gram, rows=True):
+    """The covariance of a Gauss-Newton fit and its image on every row of J, per sample in float64: from the
+    Jacobian stack ``T`` of a decode sweep and ``gram`` (B, d, d) float32 -- any normal matrix a step kernel consumes: the ``jtj``
+    of one ``gram_cholesky`` attempt, the ``gram`` of ``weighted_gauss_newton_step``, or the Gram matrix of a measured stack; the
+    lower triangles are read --, cov = gram^-1 and lev_i = j_i^T cov j_i over the first d columns of ``T``.  With ``rows=False``
+    only ``cov`` and ``info`` are computed (the same bits) and ``T`` is not read.  Returns a ``LeverageResult``.  Deterministic
+    per sample; one launch, no synchronisation."""
+    _check_tangent(T)
+    B, d = _gram_stack(gram, "B", "the leverage kernel supports", PROJECT_MAX_WIDTH)
+    dev = gram.device
+    if T.B != B or T.nc % 16 or T.nc < d or T.data.device != dev:
+        raise ValueError(f"T (B = {T.B}, N = {T.N}, nc = {T.nc}) on {T.data.device} must hold d = {d} <= nc columns, nc % 16 == 0, "
+                         f"for the {B} samples of jtj {tuple(gram.shape)} on {dev}")
+    n = T.N
+    r = LeverageResult()
+    r.cov = torch.empty(B, d, d, dtype=torch.float64, device=dev)
+    r.lev = torch.empty(B, n, dtype=torch.float64, device=dev) if rows else None
+    r.stats = torch.empty(B, 2, dtype=torch.float64, device=dev) if rows else None
+    r.info = torch.empty(B, dtype=torch.int32, device=dev)
+    if B == 0:
+        return r
+    if rows:
+        launch = lambda: _lib.check(_lib.load().cmf_tangent_leverage(_p(T.data), T.t_b, T.t_r, n, T.nc, d, B, _p(gram), _p(r.cov),
+                                                                     _p(r.lev), _p(r.stats), _p(r.info), _stream()),
+                                    "cmf_tangent_leverage")
+    else:
+        launch = lambda: _lib.check(_lib.load().cmf_tangent_leverage(None, 0, 0, 0, 0, d, B, _p(gram), _p(r.cov), None, None,
+                                                                     _p(r.info), _stream()), "cmf_tangent_leverage")
+
+    def cost():
+        # float64: the elimination d^3 / 3, the inverse of the unit factor d^3 / 3, cov d^3 / 2 (three operations per term of a
+        # d^3 / 6 sum) and, per row, d^2 / 2 multiply-adds with 3 d for the squares; bytes: the live quarter-rows of J once, the
+        # triangle of gram in, cov and lev out, stats and info
+        ncl = min(T.nc, -(-d // 4) * 4)
+        nr = n if rows else 0
+        return (B * (7.0 * d ** 3 / 6.0 + nr * (1.0 * d * d + 3.0 * d)),
+                B * (4.0 * nr * ncl + 2.0 * d * (d + 1) + 8.0 * d * d + 8.0 * nr + (16.0 if rows else 0.0) + 4.0))
+    _timed("tangent_leverage", cost, launch)
+    return r
+
+
 def _operator_pair(a, xhat):
     """The checks ``operator_apply`` and ``operator_image`` share; returns (B, M, D)."""
     _check_tensor("a", a, torch.float32, "(M, D)", lambda t: t.dim() == 2 and t.shape[0] >= 1 and t.shape[1] >= 1)

@@ -12,6 +12,7 @@ started at the encoder's latent.  A step is one decode sweep (x_hat, J), the Gra
     proj.complete(x.cuda(), weights)                    # the same with missing or unevenly trusted elements
     proj.recover(y, A, x_init=x0.cuda())                # the same seen through a linear measurement y = A x
     proj.recover(y, A, x_init=x0.cuda(), space="data")  # A acts on the density's input, e.g. pixel values
+    proj.uncertainty(out, operator=A, space="data")     # error bars on any of these answers
 """
 import torch
 
@@ -99,6 +100,38 @@ def data_space_wrapper(chain):
 def join_parts(parts):
     """The result dicts of a call's sub-batches as one dict, concatenated along the leading dimension."""
     return parts[0] if len(parts) == 1 else {k: torch.cat([p[k] for p in parts]) for k in parts[0]}
+
+
+def refuse(name, t, want, fits):
+    """``recover``'s and ``uncertainty``'s rule for a float32 argument -- dtype, shape, contiguity: said before the device is looked at."""
+    if not isinstance(t, torch.Tensor) or t.dtype != torch.float32 or not fits(t) or not t.is_contiguous():
+        raise ValueError(f"{name} must be a contiguous float32 {want} tensor, got {getattr(t, 'dtype', type(t).__name__)} "
+                         f"{tuple(getattr(t, 'shape', ()))}"
+                         f"{' (not contiguous)' if isinstance(t, torch.Tensor) and not t.is_contiguous() else ''}")
+
+
+def noise_level(n_obs, d, cost=None, variance=None):
+    """(sigma^2 (B,) float64, dof (B,) int32) of a least-squares fit of ``d`` parameters to ``n_obs`` (B,) observations: dof =
+    n_obs - d and sigma^2 = ``variance`` where the caller knows it, else the residual estimate ``cost`` / dof -- NaN where dof <=
+    0, set by ``torch.where`` on the tensors' own device (no look at the values)."""
+    dof = (n_obs - d).to(torch.int32)
+    if variance is not None:
+        return variance, dof
+    nan = torch.full_like(cost, float("nan"))
+    return torch.where(dof > 0, cost / dof.clamp_min(1).to(cost.dtype), nan), dof
+
+
+def wrapper_derivative(triple, x_hat):
+    """|du/dv| (B, D) float32 at the head-space values ``x_hat`` of the fused pre-head v = [logit](wa x + wc) of ``triple`` (wa, wc,
+    logit): (p (1 - p) if logit else 1) / |wa| with p the sigmoid of v, elementwise in float64 and through e = exp(-|v|) as the
+    operator kernel forms it, p (1 - p) = e / (1 + e)^2 -- what ``engine.operator_apply_wrapped`` leaves in ``scale``,
+    for the calls that run no operator kernel."""
+    wa, _, logit = triple
+    v = x_hat.flatten(1).double()
+    if logit:
+        e = torch.exp(-v.abs())
+        return (e / (1.0 + e) ** 2 / abs(wa)).float()
+    return torch.full_like(v, 1.0 / abs(wa)).float()
 
 
 def lm_loop(state, cost, lam, steps, up, down, trial):
@@ -324,12 +357,6 @@ class ManifoldProjector:
         for n in self.head.x_shape:
             D *= int(n)
 
-        def refuse(name, t, want, fits):                              # dtype, shape, contiguity: said before the device is looked at
-            if not isinstance(t, torch.Tensor) or t.dtype != torch.float32 or not fits(t) or not t.is_contiguous():
-                raise ValueError(f"{name} must be a contiguous float32 {want} tensor, got {getattr(t, 'dtype', type(t).__name__)} "
-                                 f"{tuple(getattr(t, 'shape', ()))}"
-                                 f"{' (not contiguous)' if isinstance(t, torch.Tensor) and not t.is_contiguous() else ''}")
-
         refuse("operator", operator, f"(M, {D})", lambda t: t.dim() == 2 and t.shape[0] >= 1 and t.shape[1] == D)
         M, dev = operator.shape[0], operator.device
         refuse("measurements", measurements, f"(B, {M})", lambda t: t.dim() == 2 and t.shape[1] == M)
@@ -397,3 +424,137 @@ class ManifoldProjector:
         return {"latent": z, "reconstruction_head": x_hat, "reconstruction": to_data_space(self.chain, x_hat), "measurement": y_hat,
                 "cost": c, "initial_cost": c_0, "tangential2": r.stats[:, 1].contiguous(), "gradient": r.grad,
                 "accepted": accepted, "damping": lam, "info": r.info}
+
+    @torch.no_grad()
+    def uncertainty(self, result, weights=None, operator=None, space="head", noise_std=None):
+        """Error bars of a fit: the classical first-order covariance of the nonlinear least-squares estimate that
+        ``project``, ``complete`` or ``recover`` returned, under the model y = A u(g(z_0)) + eps with independent eps_i ~ N(0,
+        sigma^2 / w_i) -- A the identity and w = 1 where the call had neither.  With J the decoder's Jacobian at the returned
+        latent and N the call's normal matrix (J^T J, J^T diag(w) J, or K^T K with K = A diag(du/dv) J),
+            cov(z) = sigma^2 N^-1,     var(g(z)_i) = sigma^2 j_i^T N^-1 j_i     (the delta method),
+        computed per sample in float64 by one decode sweep, the call's own Gram kernel and ``engine.tangent_leverage``.
+          ``result``: the dict of the call being qualified; ``latent`` is read, and -- with ``noise_std`` None -- ``cost``, or
+          ``distance2`` where there is no ``cost``.  ``weights``: exactly as ``complete`` took them (shape, dtype, device, carried
+          through ``to_head_space_weights``).  ``operator``, ``space``: exactly as ``recover`` took them (the same refusals; for
+          "data" the same ``data_space_wrapper`` and column permutation).  Giving both ``weights`` and ``operator`` is a ValueError.
+          ``noise_std``: sigma, the noise standard deviation per unit weight in the space the cost is measured in; a float >= 0
+          or a (B,) floating point tensor on the device (a negative entry gives that sample NaN, on the device).  None: sigma^2 is
+          estimated as cost / dof with dof = n_obs - d, n_obs = D for ``project``, the sample's count of w > 0 for ``complete``,
+          M for ``recover``; NaN where dof <= 0.
+        Returns device tensors: ``latent_covariance`` (B, d, d) float64 = sigma^2 N^-1; ``latent_std`` (B, d) float64, the root of
+        its diagonal; ``leverage`` (B, *x_shape) float64 = j_i^T N^-1 j_i; ``reconstruction_std_head`` (B, *x_shape) float32 =
+        sigma sqrt(leverage); with ``space`` = "data" also ``reconstruction_std`` (B, *data shape) float32 = |du/dv| times the
+        head-space value, mapped back through the wrapper's index map (the delta method once more); ``noise_variance`` (B,)
+        float64; ``dof`` (B,) int32; ``info`` (B,) int32, the kernel's: 0, 1 a singular normal matrix, 2 a non-finite input
+        (covariance and leverage NaN in both cases).
+        What the numbers are: the uncertainty of the MANIFOLD POINT, not a predictive interval for a new noisy observation
+        (which would add sigma^2 / w_i).  An element the fit never saw (w_i = 0, or outside A's support) gets a finite value: how
+        well the observed ones pin it down through the manifold.  With M < d, or fewer observed elements than d, the normal
+        matrix is singular: ``info`` = 1 and NaN -- a result, as in ``recover``.  The covariance is first order: on ReLU
+        couplers J is the Jacobian of the current linear piece and kinks are ignored (the caveat of DESIGN 4.3h), and no prior on
+        z enters.
+        Sub-batches like ``project``; enqueues kernels only -- no copy to the host --, modifies no input and leaves
+        ``head.last_gram`` alone."""
+        prog = self.head.program
+        d = prog.d
+        if space not in ("head", "data"):
+            raise ValueError(f"space must be 'head' or 'data', got {space!r}")
+        if weights is not None and operator is not None:
+            raise ValueError("give weights (the problem of complete) or operator (the problem of recover), not both")
+        wrapper = data_space_wrapper(self.chain) if space == "data" else None
+        D = 1
+        for n in self.head.x_shape:
+            D *= int(n)
+        latent = result.get("latent") if isinstance(result, dict) else None
+        refuse("result['latent']", latent, f"(B, {d})", lambda t: t.dim() == 2 and t.shape[1] == d)
+        B, dev = latent.shape[0], latent.device
+        if B == 0:
+            raise ValueError("uncertainty needs at least one sample, got 0")
+        cost = variance = None
+        if noise_std is None:
+            cost = result.get("cost", result.get("distance2"))
+            if not isinstance(cost, torch.Tensor) or cost.dtype != torch.float64 or tuple(cost.shape) != (B,):
+                raise ValueError(f"result['cost'] (or 'distance2') must be a float64 ({B},) tensor when noise_std is None, got "
+                                 f"{getattr(cost, 'dtype', type(cost).__name__)} {tuple(getattr(cost, 'shape', ()))}")
+        elif isinstance(noise_std, torch.Tensor):
+            if not noise_std.is_floating_point() or tuple(noise_std.shape) != (B,):
+                raise ValueError(f"noise_std must be a float or a floating point ({B},) tensor, got {noise_std.dtype} "
+                                 f"{tuple(noise_std.shape)}")
+        elif not float(noise_std) >= 0:
+            raise ValueError(f"noise_std must be >= 0, got {noise_std}")
+        data_shape = None
+        if weights is not None:
+            if not isinstance(weights, torch.Tensor) or not (weights.is_floating_point() or weights.dtype == torch.bool):
+                raise ValueError(f"weights must be a floating point or bool tensor, got "
+                                 f"{getattr(weights, 'dtype', type(weights).__name__)}")
+            data_shape = self.data_shape()
+            if tuple(weights.shape) not in ((B, *data_shape), data_shape, (1, *data_shape)):
+                raise ValueError(f"weights must have x's shape {(B, *data_shape)} or broadcast over its batch, got "
+                                 f"{tuple(weights.shape)}")
+            to_head_space_weights(self.chain, torch.empty(1, *data_shape))             # refuses what cannot be mapped
+        if operator is not None:
+            refuse("operator", operator, f"(M, {D})", lambda t: t.dim() == 2 and t.shape[0] >= 1 and t.shape[1] == D)
+        for name, v in (("result['cost']", cost), ("noise_std", noise_std), ("weights", weights), ("operator", operator)):
+            if isinstance(v, torch.Tensor) and v.device != dev:
+                raise ValueError(f"{name} must be on result['latent']'s device {dev}, got {v.device} (there is no CPU fallback)")
+        E._check_on_gpu("result['latent']", latent)
+        if noise_std is not None:
+            ns = noise_std.double() if isinstance(noise_std, torch.Tensor) else torch.full((B,), float(noise_std),
+                                                                                         dtype=torch.float64, device=dev)
+            variance = torch.where(ns >= 0, ns * ns, torch.full_like(ns, float("nan")))
+        if wrapper is not None:
+            data_shape = self.data_shape() if data_shape is None else data_shape
+            if operator is not None and wrapper[3] is not None:
+                operator = operator.index_select(1, wrapper[3].to(dev))   # acts on head-ordered elements; a copy
+        w = None if weights is None else weights.to(torch.float32).expand(B, *data_shape)
+        chunk = prog.tangent_chunk(B)
+        pick = lambda t, i: None if t is None else t[i:i + chunk]
+        with E.scope(self.head.kernels):
+            parts = [self._uncertainty(latent[i:i + chunk], pick(w, i), operator, wrapper, data_shape, pick(cost, i),
+                                       pick(variance, i)) for i in range(0, B, chunk)]
+        return join_parts(parts)
+
+    def data_shape(self):
+        """The shape of one sample of the density's input: the head's ``x_shape`` taken back through the reshaping bijections of
+        the wrapper chain (elementwise ones keep the shape)."""
+        shape = tuple(int(n) for n in self.head.x_shape)
+        for bijection in reversed(self.chain):
+            if isinstance(bijection, (ViewBijection, Squeeze2dBijection)):
+                shape = tuple(int(n) for n in bijection.x_shape)
+        return shape
+
+    def _uncertainty(self, z, w, a, wrapper, data_shape, cost, variance):
+        prog = self.head.program
+        d, Bc, dev = prog.d, z.shape[0], z.device
+        x_hat, T = prog.decode(z.contiguous(), tangents=True)
+        x_hat = x_hat.contiguous()
+        scale = None
+        if w is not None:
+            w = to_head_space_weights(self.chain, w).reshape(x_hat.shape).contiguous()
+            # the residual is zero: only gram is used, and it is valid at info 1 (engine.WeightedGaussNewtonResult)
+            gram = E.weighted_gauss_newton_step(T, w, x_hat, x_hat, torch.zeros(Bc, dtype=torch.float64, device=dev), d=d).gram
+            n_obs = (w > 0).flatten(1).sum(1)
+        elif a is not None:
+            if wrapper is None:
+                K = E.operator_apply(T, a, x_hat)[0]
+            else:
+                K, _, scale = E.operator_apply_wrapped(T, a, x_hat, wrapper[:3])
+            gram = E.gram_cholesky(K, d, 1).jtj
+            n_obs = torch.full((Bc,), a.shape[0], dtype=torch.int64, device=dev)
+        else:
+            gram = E.gram_cholesky(T, d, 1).jtj
+            n_obs = torch.full((Bc,), T.N, dtype=torch.int64, device=dev)
+        r = E.tangent_leverage(T, gram)                               # on the sweep's J, whatever the normal matrix came from
+        sigma2, dof = noise_level(n_obs, d, cost, variance)
+        cov = sigma2[:, None, None] * r.cov
+        std_head = (sigma2[:, None] * r.lev).sqrt().float()
+        out = {"latent_covariance": cov, "latent_std": torch.diagonal(cov, dim1=1, dim2=2).sqrt(),
+               "reconstruction_std_head": std_head.view(x_hat.shape), "leverage": r.lev.view(x_hat.shape),
+               "noise_variance": sigma2, "dof": dof, "info": r.info}
+        if wrapper is not None:
+            s = scale.abs() if scale is not None else wrapper_derivative(wrapper[:3], x_hat)
+            std = std_head * s.view(Bc, -1)
+            if wrapper[3] is not None:                                # head element r is data element perm[r]
+                std = torch.empty_like(std).index_copy_(1, wrapper[3].to(dev), std)
+            out["reconstruction_std"] = std.view(Bc, *data_shape)
+        return out

@@ -515,6 +515,29 @@ int cmf_operator_apply(const float* a, int M, int D, const float* t, long long t
 int cmf_operator_apply_wrapped(const float* a, int M, int D, const float* t, long long t_b, long long t_r, int nc, int B,
                                const float* xhat, float wa, float wc, int logit, float* scale, float* k, long long k_b,
                                long long k_r, float* yhat, void* stream);
+/* The covariance of a Gauss-Newton fit carried back over the rows of the Jacobian, per sample in float64:
+ *   cov = gram^-1,   lev[i] = j_i^T gram^-1 j_i  for every row j_i (the first d columns of row i of t),
+ *   stats = { sum_i lev[i], max_i lev[i] }.
+ *   t, t_b, t_r, n_rows, nc, d: the Jacobian stack as cmf_gauss_newton_step takes it (both layouts through the two strides);
+ *     columns d .. nc - 1 are padding whose contents, NaN included, reach no output.
+ *   gram [B][d][d] float32: any symmetric positive definite normal matrix in the form a step kernel consumes it -- the jtj of one
+ *     cmf_gram_cholesky attempt, the gram of cmf_weighted_gauss_newton_step, or the Gram matrix of a measured stack k.  Only the
+ *     lower triangle i >= j is read, nothing is written; it need not be the Gram matrix of this t.
+ *   cov [B][d][d] float64, symmetric bit for bit;  lev [B][n_rows] float64, every value >= +0.0 (a sum of squares over positive
+ *     pivots);  stats [B][2] float64.
+ *   The elimination is that of cmf_gauss_newton_step, undamped (Cholesky in LDS, pivots only); the unit-lower factor is inverted
+ *     in place and lev[i] = sum_k y_k^2 / p_k with y = L^-1 j_i.
+ *   info [B] int32: 0 ok; 1 a pivot was not positive and finite (cov, lev, stats are NaN); 2 a non-finite value in the lower
+ *     triangle of gram or in the first d columns of t (every output is NaN; 2 wins over 1).
+ * Covariance-only mode, t == NULL: only cov and info are written -- the same bits as the full mode gives for finite t; t_b, t_r,
+ *   n_rows, nc, lev and stats are ignored.
+ * A sample's outputs are a function of its own inputs and of (n_rows, nc, d) alone: no atomics, independent of B, of its position
+ * in the batch and of the order in which workgroups finish, and they repeat bit for bit.
+ * Always: 1 <= d <= 128 (the float64 factor lives in LDS), B >= 1, gram, cov, info not NULL, cov 8-byte aligned; with t: lev,
+ * stats not NULL and 8-byte aligned, n_rows >= 1, nc % 16 == 0, d <= nc, t_b and t_r >= nc and % 4 == 0, t 16-byte aligned.
+ * Anything else: CMF_EINVAL before any launch.  No allocation, no synchronisation.                                           */
+int cmf_tangent_leverage(const float* t, long long t_b, long long t_r, int n_rows, int nc, int d, int B, const float* gram,
+                         double* cov, double* lev, double* stats, int* info, void* stream);
 /* One damped Gauss-Newton step on whole discretised curves with fixed end points.  A curve has `points` = P >= 3
  * points, N = P - 1 segments and M = P - 2 interior points; samples are curve-major: point i of curve c is sample c P + i of the
  * Jacobian stack t, of jtj and of xhat.  With r_i = xhat_{i+1} - xhat_i:
