@@ -110,7 +110,8 @@ SIGNATURES = {
     "cmf_gram_spectrum": (_i, [_fp, _i, _i, _fp, _fp, _fp, _fp, _fp]),
     "cmf_gauss_newton_step": (_i, [_fp, _ll, _ll, _i, _i, _i, _i, _fp, _fp, _fp, _fp, _fp, _fp, _fp, _fp, _fp]),
     "cmf_weighted_gauss_newton_step": (_i, [_fp, _ll, _ll, _i, _i, _i, _i, _fp, _fp, _fp, _fp, _fp, _fp, _fp, _fp, _fp, _fp]),
-    "cmf_operator_apply": (_i, [_fp, _i, _i, _fp, _ll, _ll, _i, _i, _fp, _fp, _ll, _ll, _fp, _fp]),
+    "cmf_robust_weights": (_i, [_fp, _fp, _fp, _i, _i, _i, _d, _fp, _fp, _fp, _fp, _fp]),
+    "cmf_operator_apply": (_i,[_fp, _i, _i, _fp, _ll, _ll, _i, _i, _fp, _fp, _ll, _ll, _fp, _fp]),
     "cmf_operator_apply_wrapped": (_i, [_fp, _i, _i, _fp, _ll, _ll, _i, _i, _fp, _f, _f, _i, _fp, _fp, _ll, _ll, _fp, _fp]),
     "cmf_tangent_leverage": (_i, [_fp, _ll, _ll, _i, _i, _i, _i, _fp, _fp, _fp, _fp, _fp, _fp]),
     "cmf_cross_gram": (_i, [_fp, _ll, _ll, _i, _i, _i, _i, _i, _fp, _fp]),

@@ -1153,6 +1153,61 @@ def weighted_gauss_newton_step(T, w, x, xhat, damping, d=None):
     return r
 
 
+#: the losses ``robust_weights`` takes, in the kernel's numbering
+ROBUST_LOSSES = {"huber": 0, "tukey": 1}
+#: radix passes of the exact median: eight bytes of a float64 key (csrc/robust_weights.hip)
+ROBUST_SELECT_PASSES = 8
+
+
+class RobustWeightsResult:
+    """Outputs of ``robust_weights`` (all on the device): ``w`` x's shape float32 = prior * omega (None with ``weights_out=False``),
+    ``scale`` (B,) float64 = s, ``cost`` (B,) float64 = 2 s^2 sum prior rho(r / s), ``used`` (B,) float64 = the count of elements
+    with prior > 0 (a whole number), ``effective`` (B,) float64 = sum omega over them, ``info`` (B,) int32 (0 ok; 2 a negative or
+    non-finite prior or a non-finite value at a used element: everything NaN; 3 a scale that is not finite or not > 0: everything
+    NaN but ``scale``).  The four float64 fields are views of one (B, 4) tensor, ``stats``."""
+    __slots__ = ("w", "stats", "scale", "cost", "used", "effective", "info")
+
+
+def robust_weights(x, xhat, loss, tuning, prior=None, scale=None, weights_out=True):
+    """The robust scale, IRLS weights and robust cost of the residual x - xhat per sample, in float64: s = ``scale``
+    (B,) float64 where given, else 1.4826 x the exact lower median of |x - xhat| over the elements with ``prior`` > 0 (``prior``
+    None: all, weight 1); w = prior * omega((x - xhat) / s) for ``loss`` "huber" or "tukey" with the constant ``tuning`` > 0.
+    Elements with prior == 0 are not read.  Returns a ``RobustWeightsResult``.  Deterministic per sample; one launch, no
+    synchronisation."""
+    B, n = _residual_pair(x, xhat)
+    dev = x.device
+    if prior is not None:                                             # the rule of ``_weighted_triple``, under this argument's name
+        _check_tensor("prior", prior, torch.float32, f"({B}, ...) of {n} elements per sample", lambda t: t.dim() >= 2 and
+                      t.shape[0] == B and t.numel() == B * n, dev)
+    if loss not in ROBUST_LOSSES:
+        raise ValueError(f"loss must be one of {sorted(ROBUST_LOSSES)}, got {loss!r}")
+    if not float(tuning) > 0:
+        raise ValueError(f"tuning must be > 0, got {tuning}")
+    if scale is not None:
+        _check_tensor("scale", scale, torch.float64, f"({B},)", lambda t: tuple(t.shape) == (B,), dev)
+    r = RobustWeightsResult()
+    r.w = torch.empty_like(x) if weights_out else None
+    r.stats = torch.empty(B, 4, dtype=torch.float64, device=dev)
+    r.scale, r.cost, r.used, r.effective = (r.stats[:, k] for k in range(4))
+    r.info = torch.empty(B, dtype=torch.int32, device=dev)
+    if B == 0:
+        return r
+    launch = lambda: _lib.check(_lib.load().cmf_robust_weights(
+        _p(x), _p(xhat), _p(prior), n, B, ROBUST_LOSSES[loss], float(tuning), _p(scale), _p(r.w), _p(r.stats), _p(r.info), _stream()),
+        "cmf_robust_weights")
+
+    def cost():
+        # per used element and pass: the float64 difference and its key (3); the weights pass a division and about ten more.
+        # Bytes: prior (where there is one), x and xhat once per pass -- the validating pass, the select passes after the first
+        # (it shares the validating pass) and the weights pass; HBM sees them once, the rest is L2 --, w out, the outputs
+        passes = 2 + (0 if scale is not None else ROBUST_SELECT_PASSES - 1)
+        used = float(B * n) if prior is None else float((prior > 0).sum())     # a host look: under a timer only
+        return (used * (3.0 * passes + 12.0),
+                passes * ((0.0 if prior is None else 4.0 * B * n) + 8.0 * used) + (4.0 * B * n if weights_out else 0.0) + 36.0 * B)
+    _timed("robust_weights", cost, launch)
+    return r
+
+
 class LeverageResult:
     """Outputs of ``tangent_leverage`` (all on the device): ``cov`` (B, d, d) float64 = gram^-1, symmetric bit for bit, ``lev``
     (B, N) float64 = j_i^T gram^-1 j_i >= +0.0 per row of J, ``stats`` (B, 2) float64 = [sum_i lev_i, max_i lev_i] (both None

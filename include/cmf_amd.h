@@ -481,6 +481,26 @@ int cmf_gauss_newton_step(const float* t, long long t_b, long long t_r, int n_ro
 int cmf_weighted_gauss_newton_step(const float* t, long long t_b, long long t_r, int n_rows, int nc, int d, int B,
                                    const float* w, const float* x, const float* xhat, const double* damping, float* gram,
                                    double* grad, double* delta, double* stats, int* info, void* stream);
+/* Robust scale, IRLS weights and robust cost of a residual, per sample: what turns the weighted projection into
+ * one that finds its own outliers.  In float64 on r_i = (double)x_i - (double)xhat_i over the USED elements, prior_i > 0:
+ *   s = scale_in[b], or (scale_in == NULL) 1.4826 med with med the LOWER median of |r_i| over the m used elements -- the order
+ *     statistic of 0-based rank (m - 1) / 2, exact for any n_rows (a radix select on the bit patterns; -0.0 counts as +0.0);
+ *   u_i = r_i / s;  loss 0, Huber:  omega = |u| <= c ? 1 : c / |u|,  rho = |u| <= c ? u^2 / 2 : c |u| - c^2 / 2;
+ *                   loss 1, Tukey:  t = max(0, 1 - (u / c)^2),  omega = t^2,  rho = (c^2 / 6) (1 - t^3);   c = tuning;
+ *   w[b][i] = float(prior_i omega_i), exactly 0.0f where prior_i == 0;
+ *   stats[b] = { s, 2 s^2 sum_i prior_i rho_i, m, sum_i omega_i } -- the cost is sum_i prior_i r_i^2 where nothing is down-weighted.
+ *   x, xhat [B][n_rows] float32, contiguous.  prior [B][n_rows] float32 >= 0, or NULL for all 1: the known weights of
+ *     cmf_weighted_gauss_newton_step.  An element with prior == 0 is never read in x or xhat -- they may hold anything there, NaN
+ *     included, and reach no output.  w [B][n_rows] float32, or NULL: cost-only mode, the same stats and info bits.
+ *   info [B] int32: 0 ok; 2 a prior that is negative or not finite, or a non-finite x or xhat at a used element (w and stats are
+ *     NaN); 3 s is not finite or not > 0 -- no used element (the median of nothing is NaN), a zero median, a bad scale_in -- (w
+ *     and stats are NaN, except stats[0] = s).  NaN weights make cmf_weighted_gauss_newton_step report info 2.
+ * A sample's outputs are a function of its own inputs and of n_rows alone: the sums run in a fixed order, there are no
+ * floating-point atomics, and they are independent of B, of the sample's position in the batch and repeat bit for bit.
+ * n_rows, B >= 1; x, xhat, stats, info not NULL; loss 0 or 1; tuning > 0; float64 pointers 8-byte aligned.  Anything else:
+ * CMF_EINVAL, and nothing is launched.  No allocation, no synchronisation.                                                       */
+int cmf_robust_weights(const float* x, const float* xhat, const float* prior, int n_rows, int B, int loss, double tuning,
+                       const double* scale_in, float* w, double* stats, int* info, void* stream);
 /* A linear measurement operator carried through one decode sweep: for the recovery min_z ||y - a g(z)||^2.
  *   k(b, m, c) = sum_i a[m][i] t(b, i, c)  for every column c < nc  (the Jacobian stack K_b = a J_b of M rows),
  *   yhat[b][m] = fl32(sum_i a[m][i] xhat[b][i]).
